@@ -6,8 +6,14 @@ seed = rank, resident in HBM. One STEP = encrypt + decrypt of the whole tensor, 
 ConvertToFixedPoint (fp32 -> int64 mantissa + int64 exponent) followed by FixedPointToFloatPoint
 (back to fp32), both through libefl_hip.so's C ABI (efls-train/cc/efl/math/fixed_point.cc).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit,
+ms_per_step, ...): nothing else. --dump-outputs DIR then also writes what the last timed step
+computed (mantissa, exponent, decoded) as DIR/<name>.npy. Everything below that is not the headline
+figure (the round-trip gate, roofline, per-kernel times, cpu_baseline, config3 / pinned_path /
+config5) runs only with --full.
 
 value = (N x 0.25 GiB) / (max over ranks of the time of K steps / K)        [GiB/s, weak scaling]
 Multi-GPU: every rank owns its own 256 MiB shard (the path is element-wise: no payload exchange);
@@ -15,14 +21,14 @@ the only collective is the broadcast of the 32-byte key seed from rank 0 (timed 
 every rank has its own GPU, gloo when ranks share one (efl.distributed.choose_backend).
 
 The timed region holds nothing but the K steps (no events, no host work between launches).
-roofline: per-kernel average durations come from a second pass of K steps right after it, with HIP
+roofline (--full): per-kernel average durations come from a second pass of K steps right after it, with HIP
 events recorded around every launch on the stream the kernels run on. Algorithmic bytes:
 20 B/element per kernel (encode: 4 read + 16 written; decode: 16 read + 4 written), SURVEY.md §8(d).
 Decode runs in the reference's TF-runtime rounding mode (FTZ, efl.lib.flush_denormal()).
-cpu_baseline: the reference CPU op (oracle/: the literal encode loop of fixed_point.cc:107-137 +
+cpu_baseline (--full): the reference CPU op (oracle/: the literal encode loop of fixed_point.cc:107-137 +
 the GMP mpf decode of :235-248, FTZ|DAZ like a TF threadpool thread, contiguous blocks like TF
 Shard over every usable host core) timed on this box on the same tensor (rank 0, N = 1 only).
-Extra keys at N = 1: "config3" (BASELINE config 3: 4096 x 64 KiB slices, one batched launch per
+Extra keys at N = 1 (--full): "config3" (BASELINE config 3: 4096 x 64 KiB slices, one batched launch per
 direction, and the naive per-slice launches), "pinned_path" (the north_star's rate including
 pinned H2D/D2H copies: efl.framework.host_pipeline over the same tensor, encrypt leg pinned fp32 ->
 pinned M+E, decrypt leg back) and "config5" (the two-process gRPC loopback end to end,
@@ -81,8 +87,17 @@ def parse(argv=None):
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--backend", choices=("nccl", "gloo"), default=None,
                    help="process-group backend for N > 1 (default: nccl if every rank has a GPU)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-extras", action="store_true", help="skip the config3 / pinned_path keys")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: the round-trip gate, per-kernel "
+                        "times and roofline, rank devices, d2d copy, config3 / pinned_path / config5, "
+                        "cpu_baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last step computed as DIR/<name>.npy "
+                        "(a fixed seeded sample when the outputs exceed 64 MB)")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full or --stage p: skip cpu_baseline")
+    p.add_argument("--no-extras", action="store_true",
+                   help="with --full: skip the config3 / pinned_path / config5 keys")
     p.add_argument("--cpu-threads", type=int,
                    default=int(os.environ["EFL_BENCH_CPU_THREADS"]) if os.environ.get("EFL_BENCH_CPU_THREADS")
                    else None, help="CPU baseline threads (default: every usable core)")
@@ -109,6 +124,29 @@ def broadcast_seed(world, rank):
     if torch.cuda.is_available():
         torch.cuda.synchronize()
     return seed, (time.perf_counter() - t0) / 10 * 1e6
+
+
+DUMP_MAX_BYTES = 60 * 10**6    # --dump-outputs: every rank's files together stay below 64 MB
+DUMP_BYTES_PER_ELEM = 8 + 8 + 4   # mantissa, exponent as float64 (exact: |int64| values < 2^53), decoded fp32
+
+
+def dump_outputs(path, M, E, y, rank, world):
+    """--dump-outputs: what the last timed step left in the path's output tensors, the arrays a
+    caller of encode + decode receives: mantissa and exponent (int64, written as float64) and the
+    decoded fp32 tensor, flattened. Outputs larger than the budget are sampled at the same fixed
+    element indices in all three (CPU generator, seed 0: identical from run to run and build to
+    build). Rank r of an N-rank run writes <name>_rank<r>.npy."""
+    os.makedirs(path, exist_ok=True)
+    n = y.numel()
+    keep = DUMP_MAX_BYTES // (DUMP_BYTES_PER_ELEM * world)
+    idx = None
+    if n > keep:
+        idx = torch.randint(0, n, (keep,), generator=torch.Generator().manual_seed(0)).to(y.device)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, t, dt in (("mantissa", M, np.float64), ("exponent", E, np.float64), ("decoded", y, np.float32)):
+        flat = t.reshape(-1)
+        a = (flat if idx is None else flat.index_select(0, idx)).cpu().numpy().astype(dt)
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
 
 
 def load_traffic():
@@ -757,10 +795,10 @@ def main(argv=None):
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    # correctness gate before timing: with FTZ the round trip is the identity on every bit
-    # pattern torch.randn makes (no denormals; +-0.0 -> +-0.0)
-    if not torch.equal(y.view(torch.int32), x.view(torch.int32)) if ftz else \
-            not torch.equal(y[x != 0], x[x != 0]):
+    # correctness gate before timing (--full): with FTZ the round trip is the identity on every
+    # bit pattern torch.randn makes (no denormals; +-0.0 -> +-0.0)
+    if args.full and (not torch.equal(y.view(torch.int32), x.view(torch.int32)) if ftz else
+                      not torch.equal(y[x != 0], x[x != 0])):
         raise SystemExit("bench: encode/decode round trip is wrong")
 
     # ---- timed region: K steps, nothing else -------------------------------------------------
@@ -774,6 +812,45 @@ def main(argv=None):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, M, E, y, rank, world)
+
+    def headline(elapsed):
+        ms_per_step = elapsed / args.steps * 1e3
+        return {
+            "metric": METRIC,
+            "value": round(world * (n * 4) / GIB / (elapsed / args.steps), 2),
+            "unit": "GiB/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "int64",
+            "data": "synthetic: torch.randn fp32 on device, generator seed = rank",
+            "config": {"workload": "config 2: single 256 MiB fp32 tensor [65536,1024] per GPU, "
+                                   "device-resident ConvertToFixedPoint + FixedPointToFloatPoint",
+                       "elements_per_gpu": n, "decrease_precision": False, "decode_ftz": ftz,
+                       "parallelism": f"element-wise shard, {world} x 256 MiB, {backend if world > 1 else 'no'} "
+                                      f"seed broadcast"},
+            "full": args.full,
+            "dumped_outputs": args.dump_outputs,
+            "seed_broadcast_us": round(bcast_us, 2),
+            "backend": backend if world > 1 else None,
+            "library": efl.lib.version(),
+        }
+
+    if not args.full:
+        # a plain run: the headline figure only (max over ranks of the K steps' time)
+        if world > 1:
+            elapsed, = edist.all_reduce_max([elapsed])
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(headline(elapsed)), flush=True)
+        return
 
     # ---- per-kernel durations: a second pass of K steps with HIP events on the launch stream -
     evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
@@ -793,7 +870,6 @@ def main(argv=None):
         elapsed, t_enc, t_dec = edist.all_reduce_max([elapsed, t_enc, t_dec])
 
     ms_per_step = elapsed / args.steps * 1e3
-    value = world * (n * 4) / GIB / (elapsed / args.steps)
     # every rank reports the device it really ran on (PCI location) and its own kernel times,
     # gathered after the timed region
     rank_devices = edist.gather_rank_devices({**edist.rank_device_info(rank, dev), **own})
@@ -832,23 +908,7 @@ def main(argv=None):
                           (f"; {tr['profile_dir']}" if tr.get("profile_dir") else "") +
                           (f"; library {tr['library']}" if tr.get("library") else ""))
     out = {
-        "metric": METRIC,
-        "value": round(value, 2),
-        "unit": "GiB/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "int64",
-        "data": "synthetic: torch.randn fp32 on device, generator seed = rank",
-        "config": {"workload": "config 2: single 256 MiB fp32 tensor [65536,1024] per GPU, "
-                               "device-resident ConvertToFixedPoint + FixedPointToFloatPoint",
-                   "elements_per_gpu": n, "decrease_precision": False, "decode_ftz": ftz,
-                   "parallelism": f"element-wise shard, {world} x 256 MiB, {backend if world > 1 else 'no'} "
-                                  f"seed broadcast"},
+        **headline(elapsed),
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": PEAK_HBM_GBS,
                      "unit": "GB/s", "frac": round(achieved / PEAK_HBM_GBS, 4),
                      "traffic": traffic, "traffic_source": traffic_source, "kernel": dominant,
@@ -857,12 +917,9 @@ def main(argv=None):
         "kernels_ms": {"encode": round(t_enc, 4), "decode": round(t_dec, 4)},
         "step_roofline_frac": round(2 * BYTES_PER_ELEM_KERNEL * n / (ms_per_step * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
         "d2d_copy_GBs": round(copy_gbs, 1) if copy_gbs else None,
-        "seed_broadcast_us": round(bcast_us, 2),
-        "backend": backend if world > 1 else None,
         "devices_used": edist.distinct_devices(rank_devices),
         "devices_visible": torch.cuda.device_count(),
         "rank_devices": rank_devices,
-        "library": efl.lib.version(),
         "cpu_baseline": None,
     }
     if world == 1 and not args.no_extras:

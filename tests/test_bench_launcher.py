@@ -144,7 +144,8 @@ def _gather_worker(rank, world, port, q):
 @pytest.mark.gpu
 def test_gpus2_launches_two_ranks_on_one_gpu():
     t0 = time.perf_counter()
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-extras", "--no-cpu-baseline"], timeout=110)
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline"],
+             timeout=110)
     wall = time.perf_counter() - t0
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
