@@ -1,0 +1,441 @@
+// RSA blind-signature PSI, the kernels (efl.psi; reference: efls-data/xfl/data/psi/rsa_signer.py,
+// one gmpy2.powmod(x, d, n) per ID on the server, powmod(r, e, n) * x and divm(s, r, n) on the client,
+// sha256 as the full-domain hash).
+//
+// k_rsa_sign: s = x^d mod N by CRT, an element's number mod p (then mod q) spread over G lanes in
+// radix 2^28 exactly as the Paillier decryption's number mod p^2 is (csrc/sliced28.h; one 64-lane wave
+// per workgroup, E = 64 / G elements per wave): x mod p -> x R28 -> x^dp by left-to-right sliding
+// windows over the element's odd powers in a stream-ordered scratch slab -> sp; the same for q; then
+// Garner's join h = (sp - sq) (q^-1 mod p) mod p, s = h q + sq at full width. dp and dq are the same
+// for every element, so the window walk is wave-uniform. Squarings are those of the decryption of the
+// same width: product scanning in one lane (sqr_fips1), SOS over two lanes (sos_sqr), CIOS for the
+// short slices.
+//
+// The exponent walk is NOT constant-time: its sequence of squarings and multiplies, and the table
+// entries it loads, follow the bits of dp and dq (as the reference's gmpy2.powmod does). The signer
+// is a batch service on the key owner's own machine; it is no defence against a co-tenant who can
+// time the GPU.
+//
+// k_rsa_blind: out = r^e h mod N, binary square-and-multiply over the public exponent (up to 64
+// bits) in the 32-bit sliced arithmetic of csrc/sliced.h; with e = 1 it is the product s r^-1 of the
+// unblinding (rsaset.hip composes it with the batched inversion of paillier.hip).
+// k_sha256_fdh: FIPS 180-4 SHA-256 of n packed byte strings, one lane per string, the digest as the
+// low 8 words of a row.
+#include "rsa.h"
+#include "sliced.h"
+#include "sliced28.h"
+
+namespace efl {
+namespace rsa {
+namespace {
+
+using namespace sl;
+
+constexpr int kWave = 64;
+// window width and odd-power entries of the walk: the decryption's (paillier_sliced.hip kDecWin)
+constexpr int kWin = 5, kEntries = 1 << (kWin - 1);
+// elements per launch (the slab holds kEntries + 1 numbers for each)
+constexpr long long kChunk = 1 << 18;
+
+template <int C28>
+constexpr int pad4() { return (C28 + 3) & ~3; }
+
+template <int C28>
+__device__ __forceinline__ void store28(uint32_t* q, const uint32_t (&t)[C28]) {
+  constexpr int CP = pad4<C28>();
+#pragma unroll
+  for (int j = 0; j < CP; j += 4)
+    *reinterpret_cast<uint4*>(q + j) = make_uint4(t[j], j + 1 < C28 ? t[j + 1] : 0u, j + 2 < C28 ? t[j + 2] : 0u,
+                                                  j + 3 < C28 ? t[j + 3] : 0u);
+}
+template <int C28>
+__device__ __forceinline__ void load28(uint32_t (&t)[C28], const uint32_t* q) {
+  constexpr int CP = pad4<C28>();
+#pragma unroll
+  for (int j = 0; j < CP; j += 4) {
+    const uint4 v = *reinterpret_cast<const uint4*>(q + j);
+    t[j] = v.x;
+    if (j + 1 < C28) t[j + 1] = v.y;
+    if (j + 2 < C28) t[j + 2] = v.z;
+    if (j + 3 < C28) t[j + 3] = v.w;
+  }
+}
+
+template <int C>
+__device__ __forceinline__ void from_lds(uint32_t (&x)[C], const uint32_t* base, int E, int g) {
+#pragma unroll
+  for (int j = 0; j < C; ++j) x[j] = base[(g * C + j) * E];
+}
+
+// bit b of a wave-uniform exponent
+__device__ __forceinline__ uint32_t ebit(const uint32_t* ex, int b) { return (ex[b >> 5] >> (b & 31)) & 1u; }
+
+// one squaring with the method of the family; the SOS square takes both LDS arrays (contiguous)
+template <int C28, int G, bool SOS>
+__device__ __forceinline__ void sqr(uint32_t (&a)[C28], uint32_t* BASE, uint32_t* SCR, int E,
+                                    const uint32_t (&m28)[C28], uint32_t minv28, int g) {
+  if constexpr (SOS) s28::sos_sqr<C28, G>(a, BASE, E, m28, minv28, g);
+  else s28::mont_sqr<C28, G>(a, SCR, E, m28, minv28, g);
+  lds_sync();
+}
+
+// a <- a^ex in radix-2^28 Montgomery form (lazy: < 2m), ex of ebits >= 1 bits, uniform over the
+// wave. slot: this lane's slice of the element's slab (entry k at slot + k G CP). The loop has one
+// site for its squarings (the table's c^2, a 0 bit's lone squaring, a window's run): the next step is
+// planned at its end.
+template <int C28, int G, bool SOS>
+__device__ __forceinline__ void powm_window(uint32_t (&a)[C28], uint32_t* slot, const uint32_t* ex, int ebits,
+                                            uint32_t* BASE, uint32_t* SCR, int E, const uint32_t (&m28)[C28],
+                                            uint32_t minv28, int g) {
+  constexpr int CP = pad4<C28>();
+  store28<C28>(slot, a);
+  int b = ebits - 1;
+  int j = b - kWin + 1 > 0 ? b - kWin + 1 : 0;
+  while (!ebit(ex, j)) ++j;
+  uint32_t v = 0;
+  for (int t = b; t >= j; --t) v = (v << 1) | ebit(ex, t);
+  int nsq = 1;
+  bool build = true, mul = false;
+  size_t ent_at = 0;
+#pragma unroll 1
+  for (;;) {
+#pragma unroll 1
+    for (int t = 0; t < nsq; ++t) sqr<C28, G, SOS>(a, BASE, SCR, E, m28, minv28, g);
+    if (build) {
+      // a = c^2: stage it, then the odd powers T[k] = T[k-1] c^2 from T[0] = c
+      to_lds<C28>(BASE, E, g, a);
+      lds_sync();
+      load28<C28>(a, slot);
+#pragma unroll 1
+      for (int k = 1; k < kEntries; ++k) {
+        s28::mont_mul<C28, G>(a, LdsElem{BASE, E}, m28, minv28, g);
+        store28<C28>(slot + (size_t)k * G * CP, a);
+      }
+      lds_sync();
+      load28<C28>(a, slot + (size_t)(v >> 1) * G * CP);   // the top window
+      b = j - 1;
+      build = false;
+    } else if (mul) {
+      uint32_t ent[C28];
+      load28<C28>(ent, slot + ent_at);
+      to_lds<C28>(BASE, E, g, ent);
+      lds_sync();
+      s28::mont_mul<C28, G>(a, LdsElem{BASE, E}, m28, minv28, g);
+      lds_sync();
+    }
+    if (b < 0) break;
+    if (!ebit(ex, b)) {
+      nsq = 1;
+      mul = false;
+      --b;
+    } else {
+      // a window of up to kWin bits that ends in a 1 bit
+      j = b - kWin + 1 > 0 ? b - kWin + 1 : 0;
+      while (!ebit(ex, j)) ++j;
+      v = 0;
+      for (int t = b; t >= j; --t) v = (v << 1) | ebit(ex, t);
+      ent_at = (size_t)(v >> 1) * G * CP;
+      nsq = b - j + 1;
+      mul = true;
+      b = j - 1;
+    }
+  }
+}
+
+// C 32-bit words per lane of a number mod p (L = C G words); rows of x and s have k.W words, 2 L
+// (balanced primes) or L (p or q longer than half of N's class: the high half of x is absent)
+template <int C, int G>
+__global__ __launch_bounds__(kWave, C >= 32 ? 2 : 4) void k_rsa_sign(Key k, const uint32_t* x, uint32_t* out,
+                                                                     long long N, uint32_t* win) {
+  constexpr int L = C * G, E = kWave / G;
+  constexpr int C28 = s28::limbs_per_lane(L, G), L28 = C28 * G, CP = pad4<C28>();
+  constexpr bool kSos = G == 2 && C == 32 && EFL_SQR_SOS;
+  extern __shared__ uint32_t lds[];
+  const int g = (int)threadIdx.x % G;
+  const int e = (int)threadIdx.x / G;
+  const long long i = (long long)blockIdx.x * E + e;
+  if (i >= N) return;
+  uint32_t* BASE = lds + e;
+  uint32_t* SCR = lds + L28 * E + e;            // contiguous with BASE: word L28 + w of BASE is word w of SCR
+  const bool wide = k.W == 2 * L;
+  const uint32_t* xi = x + i * k.W;
+  // this lane's slice of the element's slab: kEntries odd powers (p's, then reused for q's) and sp
+  uint32_t* slot = win + (size_t)i * (kEntries + 1) * G * CP + g * CP;
+  uint32_t* keep = slot + (size_t)kEntries * G * CP;
+  uint32_t sq[C];
+#pragma unroll 1
+  for (int second = 0; second < 2; ++second) {
+    const Prime& p0 = k.pr[0];
+    const Prime& p1 = k.pr[1];
+    const uint32_t minv = second ? p1.minv : p0.minv;
+    const uint32_t minv28 = second ? p1.minv28 : p0.minv28;
+    const uint32_t* r2 = k.at(second ? p1.off_r2 : p0.off_r2);
+    uint32_t t[C];
+    {
+      // x mod m, x = hi R + lo, R = 2^(32 L): hi R mod m = mont(hi, R^2); lo mod m = redc(mont(lo, R^2))
+      uint32_t m[C], lo[C];
+      slice_uniform<C>(m, k.at(second ? p1.off_x : p0.off_x), g);
+      load_slice<C>(lo, xi, g);
+      sl::mont_mul<C, G>(lo, Uniform{r2}, m, minv, g);
+      sl::redc<C, G>(lo, m, minv, g);
+      if (wide) {
+        load_slice<C>(t, xi + L, g);
+        sl::mont_mul<C, G>(t, Uniform{r2}, m, minv, g);
+        const uint32_t top = sl::add<C, G>(t, lo, g);
+        sl::csub<C, G>(t, m, top != 0 || sl::geq<C, G>(t, m, g), g);
+      } else {
+#pragma unroll
+        for (int j = 0; j < C; ++j) t[j] = lo[j];
+      }
+    }
+    to_lds<C>(SCR, E, g, t);
+    lds_sync();
+    // keep the 32-bit constants above from being held in VGPRs across the exponentiation
+    asm volatile("" ::: "memory");
+    uint32_t a[C28], m28[C28];
+    s28::from_words<C28>(a, SCR, E, L, g);
+    slice_uniform<C28>(m28, k.at(second ? p1.off_x28 : p0.off_x28), g);
+    lds_sync();
+    s28::mont_mul<C28, G>(a, Uniform{k.at(second ? p1.off_r2_28 : p0.off_r2_28)}, m28, minv28, g);   // x R28
+    lds_sync();
+    powm_window<C28, G, kSos>(a, slot, k.at(second ? p1.off_dx : p0.off_dx), second ? p1.dbits : p0.dbits, BASE,
+                              SCR, E, m28, minv28, g);
+    s28::mont_mul<C28, G>(a, Unit{}, m28, minv28, g);   // x^dx mod m, fully reduced
+    lds_sync();
+    to_lds<C28>(SCR, E, g, a);
+    lds_sync();
+    s28::to_words<C>(sq, SCR, E, L28, g);
+    lds_sync();
+    if (!second) store_slice<C>(keep, 0, sq);             // sp waits in the slab
+  }
+  asm volatile("" ::: "memory");
+  // Garner: h = (sp - sq) (q^-1 mod p) mod p; s = h q + sq. sq < q may exceed p (p < q, or a q
+  // longer than p): it is reduced mod p first, as hi and lo were.
+  uint32_t ph[C], d[C], r[C];
+  slice_uniform<C>(ph, k.at(k.pr[0].off_x), g);
+  const uint32_t p_minv = k.pr[0].minv;
+#pragma unroll
+  for (int j = 0; j < C; ++j) d[j] = sq[j];
+  sl::mont_mul<C, G>(d, Uniform{k.at(k.pr[0].off_r2)}, ph, p_minv, g);
+  sl::redc<C, G>(d, ph, p_minv, g);                        // sq mod p
+  load_slice<C>(r, keep, 0);                               // sp
+  if (sl::sub<C, G>(r, d, g)) sl::add<C, G>(r, ph, g);
+  sl::mont_mul<C, G>(r, Uniform{k.at(k.off_qinvp)}, ph, p_minv, g);   // h (< p, normal form)
+  // s = h q + sq by operand scanning over the words of h (in SCR); low words leave lane 0 into
+  // BASE, the high half follows them there (past L28 words it lies over the words of h already read)
+  lds_sync();
+  to_lds<C>(SCR, E, g, r);
+  lds_sync();
+  uint32_t qh[C], t[C];
+  slice_uniform<C>(qh, k.at(k.pr[1].off_x), g);
+#pragma unroll
+  for (int j = 0; j < C; ++j) t[j] = sq[j];
+  uint32_t pend = 0;
+#pragma unroll 1
+  for (int ii = 0; ii < L; ++ii) {
+    const uint32_t hv = SCR[ii * E];
+    uint32_t c1 = 0;
+#pragma unroll
+    for (int j = 0; j < C; ++j) {
+      const uint64_t p = mad(qh[j], hv, (uint64_t)t[j] + c1);
+      t[j] = (uint32_t)p;
+      c1 = (uint32_t)(p >> 32);
+    }
+    if (g == 0) BASE[ii * E] = t[0];
+    uint32_t in = from_next<G>(t[0]);
+    if (g == G - 1) in = 0;
+#pragma unroll
+    for (int j = 0; j < C - 1; ++j) t[j] = t[j + 1];
+    const uint64_t s = (uint64_t)in + pend + c1;
+    t[C - 1] = (uint32_t)s;
+    pend = (uint32_t)(s >> 32);
+  }
+  resolve_carries<C, G>(t, pend, g);
+  lds_sync();
+#pragma unroll
+  for (int j = 0; j < C; ++j) BASE[(L + g * C + j) * E] = t[j];
+  lds_sync();
+  if (wide) {
+    uint32_t o[2 * C];
+    from_lds<2 * C>(o, BASE, E, g);
+    store_slice<2 * C>(out + i * 2 * L, g, o);
+  } else {
+    uint32_t o[C];                                         // s < N < 2^(32 L): the high half is zero
+    from_lds<C>(o, BASE, E, g);
+    store_slice<C>(out + i * L, g, o);
+  }
+}
+
+// out = r^ex h mod N (ex >= 1), numbers of L = C G = k.W words over G lanes in 32-bit limbs. h and
+// r may be any W-word values: a product with an operand below N is below 2 N before its subtraction
+template <int C, int G>
+__global__ __launch_bounds__(kWave) void k_rsa_blind(Key k, const uint32_t* h, const uint32_t* r,
+                                                     uint64_t ex, uint32_t* out, long long N) {
+  constexpr int L = C * G, E = kWave / G;
+  extern __shared__ uint32_t lds[];
+  const int g = (int)threadIdx.x % G;
+  const int e = (int)threadIdx.x / G;
+  const long long i = (long long)blockIdx.x * E + e;
+  if (i >= N) return;
+  uint32_t* BASE = lds + e;
+  uint32_t* SCR = lds + L * E + e;
+  uint32_t n[C], t[C];
+  slice_uniform<C>(n, k.at(k.off_n), g);
+  const uint32_t minv = k.n_minv;
+  load_slice<C>(t, r + i * L, g);
+  sl::mont_mul<C, G>(t, Uniform{k.at(k.off_n_r2)}, n, minv, g);   // r R mod N
+  to_lds<C>(BASE, E, g, t);
+  lds_sync();
+  const int ebits = 64 - __clzll((long long)ex);
+#pragma unroll 1
+  for (int b = ebits - 2; b >= 0; --b) {
+    sl::mont_sqr<C, G>(t, SCR, E, n, minv, g);
+    if ((ex >> b) & 1ull) sl::mont_mul<C, G>(t, LdsElem{BASE, E}, n, minv, g);
+    lds_sync();
+  }
+  lds_sync();
+  to_lds<C>(SCR, E, g, t);                                        // r^e R mod N
+  lds_sync();
+  load_slice<C>(t, h + i * L, g);
+  sl::mont_mul<C, G>(t, LdsElem{SCR, E}, n, minv, g);             // h r^e mod N
+  store_slice<C>(out + i * L, g, t);
+}
+
+// ---- SHA-256 (FIPS 180-4) -----------------------------------------------------------------------
+__device__ __constant__ uint32_t kSha[64] = {
+    0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u,
+    0xd807aa98u, 0x12835b01u, 0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u,
+    0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau,
+    0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, 0x06ca6351u, 0x14292967u,
+    0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u,
+    0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u,
+    0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u,
+    0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, 0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
+
+__device__ __forceinline__ uint32_t rotr(uint32_t x, int s) { return (x >> s) | (x << (32 - s)); }
+
+// row i of out = int(sha256(string i).hexdigest(), 16): the digest is a big-endian number, so word
+// j (little-endian) is state word H[7 - j]; words 8 .. wpr - 1 are zero. One lane per string; any
+// length (a block loop, the padding in the last one or two blocks).
+__global__ __launch_bounds__(256) void k_sha256_fdh(const char* __restrict__ chars,
+                                                    const long long* __restrict__ offsets,
+                                                    uint32_t* __restrict__ out, int wpr, long long N) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const unsigned char* s = reinterpret_cast<const unsigned char*>(chars) + offsets[i];
+  const long long len = offsets[i + 1] - offsets[i];
+  const long long nblk = (len + 9 + 63) / 64;
+  uint32_t H[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu,
+                   0x5be0cd19u};
+#pragma unroll 1
+  for (long long blk = 0; blk < nblk; ++blk) {
+    uint32_t w[16];
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      uint32_t word = 0;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const long long p = blk * 64 + t * 4 + b;
+        const uint32_t byte = p < len ? s[p] : (p == len ? 0x80u : 0u);
+        word = (word << 8) | byte;
+      }
+      w[t] = word;
+    }
+    if (blk == nblk - 1) {   // the last 8 bytes lie past the 0x80 byte: the bit length
+      const unsigned long long bits = (unsigned long long)len * 8ull;
+      w[14] = (uint32_t)(bits >> 32);
+      w[15] = (uint32_t)bits;
+    }
+    uint32_t a = H[0], b = H[1], c = H[2], d = H[3], e = H[4], f = H[5], g = H[6], h = H[7];
+#pragma unroll
+    for (int t = 0; t < 64; ++t) {
+      if (t >= 16) {
+        const uint32_t w15 = w[(t + 1) & 15], w2 = w[(t + 14) & 15];
+        const uint32_t s0 = rotr(w15, 7) ^ rotr(w15, 18) ^ (w15 >> 3);
+        const uint32_t s1 = rotr(w2, 17) ^ rotr(w2, 19) ^ (w2 >> 10);
+        w[t & 15] = w[t & 15] + s0 + w[(t + 9) & 15] + s1;
+      }
+      const uint32_t S1 = rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25);
+      const uint32_t ch = (e & f) ^ (~e & g);
+      const uint32_t t1 = h + S1 + ch + kSha[t] + w[t & 15];
+      const uint32_t S0 = rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22);
+      const uint32_t mj = (a & b) ^ (a & c) ^ (b & c);
+      const uint32_t t2 = S0 + mj;
+      h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
+    }
+    H[0] += a; H[1] += b; H[2] += c; H[3] += d; H[4] += e; H[5] += f; H[6] += g; H[7] += h;
+  }
+  uint32_t* o = out + i * wpr;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = H[7 - j];
+  for (int j = 8; j < wpr; ++j) o[j] = 0u;
+}
+
+inline unsigned grid_of(long long N, int G) {
+  const long long E = kWave / G;
+  return (unsigned)((N + E - 1) / E);
+}
+
+template <int C, int G>
+hipError_t run_sign(const Key& k, const uint32_t* x, uint32_t* s, long long N, hipStream_t st) {
+  constexpr int L = C * G, C28 = s28::limbs_per_lane(L, G);
+  constexpr size_t slab = (size_t)(kEntries + 1) * G * pad4<C28>();
+  const size_t lds = (size_t)(2 * C28 * G) * (kWave / G) * 4;
+  const long long chunk = N < kChunk ? N : kChunk;
+  uint32_t* win = nullptr;
+  hipError_t err = hipMallocAsync(reinterpret_cast<void**>(&win), (size_t)chunk * slab * 4, st);
+  if (err != hipSuccess) return err;
+  for (long long o = 0; o < N && err == hipSuccess; o += chunk) {
+    const long long n = N - o < chunk ? N - o : chunk;
+    hipLaunchKernelGGL((k_rsa_sign<C, G>), dim3(grid_of(n, G)), dim3(kWave), lds, st, k, x + o * k.W, s + o * k.W, n,
+                       win);
+    err = hipGetLastError();
+  }
+  const hipError_t ferr = hipFreeAsync(win, st);
+  return err == hipSuccess ? ferr : err;
+}
+
+template <int C, int G>
+hipError_t run_blind(const Key& k, const uint32_t* h, const uint32_t* r, uint64_t e, uint32_t* out, long long N,
+                     hipStream_t st) {
+  const size_t lds = (size_t)(2 * C * G) * (kWave / G) * 4;
+  hipLaunchKernelGGL((k_rsa_blind<C, G>), dim3(grid_of(N, G)), dim3(kWave), lds, st, k, h, r, e, out, N);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+int sign_limbs28(int L) {
+  const int G = sign_lanes(L);
+  return s28::limbs_per_lane(L, G) * G;
+}
+
+hipError_t sign(const Key& k, const uint32_t* x, uint32_t* s, long long n, hipStream_t st) {
+  switch (k.L) {
+    case 16: return run_sign<8, 2>(k, x, s, n, st);
+    case 32: return run_sign<32, 1>(k, x, s, n, st);
+    case 64: return run_sign<32, 2>(k, x, s, n, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t blind(const Key& k, const uint32_t* h, const uint32_t* r, uint64_t e, uint32_t* out, long long n,
+                 hipStream_t st) {
+  if (e == 0) return hipErrorInvalidValue;
+  switch (k.W) {
+    case 32: return run_blind<32, 1>(k, h, r, e, out, n, st);
+    case 64: return run_blind<32, 2>(k, h, r, e, out, n, st);
+    case 128: return run_blind<32, 4>(k, h, r, e, out, n, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t sha256_fdh(const char* chars, const long long* offsets, uint32_t* out, int words_per_row, long long n,
+                      hipStream_t st) {
+  hipLaunchKernelGGL(k_sha256_fdh, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, chars, offsets, out,
+                     words_per_row, n);
+  return hipGetLastError();
+}
+
+}  // namespace rsa
+}  // namespace efl

@@ -7,6 +7,7 @@ Public names mirror efls-train/python/efl (exporter registry, efl/__init__.py:47
   efl.secret_sharing.{matmul, Dense, dense, share, reveal}
   efl.privacy.{DPGradientDescentGaussianOptimizer, DPAdamOptimizer, ..., make_optimizer_class}
   efl.HexTensor (the DT_STRING stand-in), efl.lib.ops (the `fed_ops` namespace)
+  efl.psi.{RsaSigner, ServerRsaSigner, ClientRsaSigner, RsaKey, pkcs1} (RSA blind-signature PSI)
 The kernels live in libefl_hip.so (C ABI: include/efl_hip.h); there is no CPU fallback.
 """
 from efl import exporter
@@ -20,6 +21,7 @@ from efl.privacy import paillier_cipher
 from efl.privacy import paillier_layer
 from efl.privacy import secret_sharing
 from efl.privacy.hex_tensor import HexTensor
+from efl import psi
 from efl.framework import communicator
 from efl.framework import encrypt_hook
 from efl.framework.communicator import Communicator, TensorHook

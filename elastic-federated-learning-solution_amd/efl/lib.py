@@ -47,6 +47,16 @@ _SIGS = {
     "efl_ss_mask_rows": ([_vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_uint64, ctypes.c_uint64, _vp], _i32),
     "efl_dp_noise": ([_vp, _vp, _i64, _i32, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _vp],
                      _i32),
+    # RSA blind-signature PSI (efl.psi; include/efl_hip.h efl_rsa_*): contexts and info structs as void*
+    "efl_rsa_ctx_create": ([_vp], _i32),
+    "efl_rsa_ctx_destroy": ([_vp], _i32),
+    "efl_rsa_set_public": ([_vp, ctypes.c_char_p, ctypes.c_char_p, _vp], _i32),
+    "efl_rsa_set_private": ([_vp] + [ctypes.c_char_p] * 5 + [_vp], _i32),
+    "efl_rsa_ctx_query": ([_vp, _vp], _i32),
+    "efl_rsa_sign": ([_vp, _vp, _vp, _i64, _vp], _i32),
+    "efl_rsa_blind": ([_vp, _vp, _vp, _vp, _i64, _vp], _i32),
+    "efl_rsa_unblind": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp], _i32),
+    "efl_sha256_fdh": ([_vp, _vp, _vp, _i32, _i64, _vp], _i32),
 }
 for _name, (_args, _ret) in _SIGS.items():
     _f = getattr(_lib, _name)

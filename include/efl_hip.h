@@ -456,6 +456,57 @@ int efl_hex_parse(const char* chars, const int64_t* offsets, int limbs_per_elem,
 int efl_pl_to_int64(const uint32_t* magnitude, int limbs_per_elem, const int8_t* negative,
                     int64_t* out, int64_t n, void* stream);
 
+/* ---- RSA blind-signature PSI (efl.psi) ------------------------------------------------------
+ * Replaces the per-ID gmpy2 calls of efls-data/xfl/data/psi/rsa_signer.py: powmod(x, d, n) of
+ * ServerRsaSigner (sign_func, sign_blinded_ids_from_client), powmod(r, e, n) * x and divm(s, r, n) of
+ * ClientRsaSigner (_blind_ids, _deblind_signed_ids), and the sha256 full-domain hash. Numbers are rows
+ * of `words` little-endian 32-bit words, words = 32, 64 or 128 for n of up to 1024, 2048, 4096 bits (a
+ * smaller n runs zero-padded in the next class); a row is also the reference's wire form
+ * int(v).to_bytes(.., 'little'), zero-extended. Rows are 16-byte aligned device memory; an input row
+ * may hold any value below 2^(32 words), it is taken mod n. An opaque context derives every constant
+ * from the hex text (csrc/rsaset.hip) and keeps them in one device block; d is used for d mod (p - 1)
+ * and d mod (q - 1) only and is never given back. Setting a key synchronises `stream`; a refused
+ * key leaves the previous one in place. */
+typedef struct efl_rsa_ctx efl_rsa_ctx;
+typedef struct {
+  int32_t has_public, has_private;
+  int32_t n_bits;
+  int32_t words;                  /* of a row */
+  int32_t byte_len;               /* n_bits / 8: the reference's wire length */
+  int32_t reserved;
+  uint64_t e;
+} efl_rsa_ctx_info;
+
+int efl_rsa_ctx_create(efl_rsa_ctx** ctx);
+/* Frees the key block (hipFree: waits for work that still reads it). */
+int efl_rsa_ctx_destroy(efl_rsa_ctx* ctx);
+/* rsa.PublicKey(n, e): hex texts; n odd, of at most 4096 bits; 1 <= e < 2^64. Drops a private key. */
+int efl_rsa_set_public(efl_rsa_ctx* ctx, const char* n_hex, const char* e_hex, void* stream);
+/* rsa.PrivateKey(n, e, d, p, q). INVALID_ARGUMENT unless p q = n, p and q odd and distinct, and
+ * e d = 1 mod (p - 1) and mod (q - 1). p < q and p > q both serve; primes longer than half of n's
+ * class (python-rsa's p) run in n's own class. */
+int efl_rsa_set_private(efl_rsa_ctx* ctx, const char* n_hex, const char* e_hex, const char* d_hex,
+                        const char* p_hex, const char* q_hex, void* stream);
+int efl_rsa_ctx_query(efl_rsa_ctx* ctx, efl_rsa_ctx_info* info);
+/* s[i] = x[i]^d mod n by CRT ([n][words] each; s may be x). ABORTED "No private key." without one.
+ * Takes stream-ordered scratch for the sliding windows' odd powers (hipMallocAsync / hipFreeAsync on
+ * `stream`, up to 2^18 elements x 17 numbers per launch). The exponent walk is not constant-time. */
+int efl_rsa_sign(efl_rsa_ctx* ctx, const uint32_t* x, uint32_t* s, int64_t n, void* stream);
+/* out[i] = r[i]^e h[i] mod n (ClientRsaSigner._blind_ids). ABORTED "No public key." without one. */
+int efl_rsa_blind(efl_rsa_ctx* ctx, const uint32_t* h, const uint32_t* r, uint32_t* out, int64_t n,
+                  void* stream);
+/* out[i] = s[i] r[i]^-1 mod n (divm(s, r, n), ClientRsaSigner._deblind_signed_ids): efl_pl_invert's
+ * batched binary GCD mod n into stream-ordered scratch, then one product. bad (device, one int64) <-
+ * -1, or the smallest index whose r has no inverse mod n (its out is 0; divm raises there); n == 0
+ * writes nothing. */
+int efl_rsa_unblind(efl_rsa_ctx* ctx, const uint32_t* s, const uint32_t* r, uint32_t* out, int64_t n,
+                    int64_t* bad, void* stream);
+/* RsaSigner.fdh as a number: row i of out ([n][words_per_row], words_per_row >= 8) =
+ * int(sha256(string i).hexdigest(), 16), for n byte strings packed back to back in `chars`, string i
+ * occupying chars[offsets[i] .. offsets[i+1]) (as efl_hex_parse takes them). Any length. */
+int efl_sha256_fdh(const char* chars, const int64_t* offsets, uint32_t* out, int words_per_row, int64_t n,
+                   void* stream);
+
 /* ---- Key generation, HOST memory (GeneratePaillierKeypairOp, paillier.cc:833-904) ------------
  * The reference's keygen is a CPU op over GMP (mpz_probab_prime_p in find_prime, :851-863;
  * mpz_powm for hs, :884-888). These two are its arithmetic, on host buffers of little-endian
