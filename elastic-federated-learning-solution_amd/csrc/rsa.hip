@@ -22,6 +22,7 @@
 // k_sha256_fdh: FIPS 180-4 SHA-256 of n packed byte strings, one lane per string, the digest as the
 // low 8 words of a row.
 #include "rsa.h"
+#include "sha256.h"
 #include "sliced.h"
 #include "sliced28.h"
 
@@ -301,22 +302,10 @@ __global__ __launch_bounds__(kWave) void k_rsa_blind(Key k, const uint32_t* h, c
   store_slice<C>(out + i * L, g, t);
 }
 
-// ---- SHA-256 (FIPS 180-4) -----------------------------------------------------------------------
-__device__ __constant__ uint32_t kSha[64] = {
-    0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u,
-    0xd807aa98u, 0x12835b01u, 0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u,
-    0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau,
-    0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, 0x06ca6351u, 0x14292967u,
-    0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u,
-    0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u,
-    0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u,
-    0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, 0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
-
-__device__ __forceinline__ uint32_t rotr(uint32_t x, int s) { return (x >> s) | (x << (32 - s)); }
-
+// ---- SHA-256 full-domain hash (the compression is sha256.h's) ---------------------------------------
 // row i of out = int(sha256(string i).hexdigest(), 16): the digest is a big-endian number, so word
 // j (little-endian) is state word H[7 - j]; words 8 .. wpr - 1 are zero. One lane per string; any
-// length (a block loop, the padding in the last one or two blocks).
+// length.
 __global__ __launch_bounds__(256) void k_sha256_fdh(const char* __restrict__ chars,
                                                     const long long* __restrict__ offsets,
                                                     uint32_t* __restrict__ out, int wpr, long long N) {
@@ -324,47 +313,8 @@ __global__ __launch_bounds__(256) void k_sha256_fdh(const char* __restrict__ cha
   if (i >= N) return;
   const unsigned char* s = reinterpret_cast<const unsigned char*>(chars) + offsets[i];
   const long long len = offsets[i + 1] - offsets[i];
-  const long long nblk = (len + 9 + 63) / 64;
-  uint32_t H[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu,
-                   0x5be0cd19u};
-#pragma unroll 1
-  for (long long blk = 0; blk < nblk; ++blk) {
-    uint32_t w[16];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-      uint32_t word = 0;
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const long long p = blk * 64 + t * 4 + b;
-        const uint32_t byte = p < len ? s[p] : (p == len ? 0x80u : 0u);
-        word = (word << 8) | byte;
-      }
-      w[t] = word;
-    }
-    if (blk == nblk - 1) {   // the last 8 bytes lie past the 0x80 byte: the bit length
-      const unsigned long long bits = (unsigned long long)len * 8ull;
-      w[14] = (uint32_t)(bits >> 32);
-      w[15] = (uint32_t)bits;
-    }
-    uint32_t a = H[0], b = H[1], c = H[2], d = H[3], e = H[4], f = H[5], g = H[6], h = H[7];
-#pragma unroll
-    for (int t = 0; t < 64; ++t) {
-      if (t >= 16) {
-        const uint32_t w15 = w[(t + 1) & 15], w2 = w[(t + 14) & 15];
-        const uint32_t s0 = rotr(w15, 7) ^ rotr(w15, 18) ^ (w15 >> 3);
-        const uint32_t s1 = rotr(w2, 17) ^ rotr(w2, 19) ^ (w2 >> 10);
-        w[t & 15] = w[t & 15] + s0 + w[(t + 9) & 15] + s1;
-      }
-      const uint32_t S1 = rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25);
-      const uint32_t ch = (e & f) ^ (~e & g);
-      const uint32_t t1 = h + S1 + ch + kSha[t] + w[t & 15];
-      const uint32_t S0 = rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22);
-      const uint32_t mj = (a & b) ^ (a & c) ^ (b & c);
-      const uint32_t t2 = S0 + mj;
-      h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
-    }
-    H[0] += a; H[1] += b; H[2] += c; H[3] += d; H[4] += e; H[5] += f; H[6] += g; H[7] += h;
-  }
+  uint32_t H[8];
+  sha256::digest(H, len, [s](long long p) { return s[p]; });
   uint32_t* o = out + i * wpr;
 #pragma unroll
   for (int j = 0; j < 8; ++j) o[j] = H[7 - j];

@@ -8,6 +8,7 @@ Public names mirror efls-train/python/efl (exporter registry, efl/__init__.py:47
   efl.privacy.{DPGradientDescentGaussianOptimizer, DPAdamOptimizer, ..., make_optimizer_class}
   efl.HexTensor (the DT_STRING stand-in), efl.lib.ops (the `fed_ops` namespace)
   efl.psi.{RsaSigner, ServerRsaSigner, ClientRsaSigner, RsaKey, pkcs1} (RSA blind-signature PSI)
+  efl.psi.EccSigner, efl.psi.ecc_cipher.{x25519, x25519_hash} (ECDH PSI: batched X25519)
 The kernels live in libefl_hip.so (C ABI: include/efl_hip.h); there is no CPU fallback.
 """
 from efl import exporter

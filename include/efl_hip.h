@@ -507,6 +507,25 @@ int efl_rsa_unblind(efl_rsa_ctx* ctx, const uint32_t* s, const uint32_t* r, uint
 int efl_sha256_fdh(const char* chars, const int64_t* offsets, uint32_t* out, int words_per_row, int64_t n,
                    void* stream);
 
+/* ---- ECDH PSI (efl.psi.EccSigner) ------------------------------------------------------------
+ * Replaces the per-ID curve25519-donna calls of efls-data/xfl/data/psi/ecc_signer.py (sign_hash for
+ * every local ID, sign for every item of the peer): X25519 of RFC 7748 with one scalar for the whole
+ * batch (csrc/fe25519.h, csrc/x25519.hip). `scalar` is 32 bytes of HOST memory, read before the call
+ * returns and clamped here (idempotent, as make_private does); it travels as kernel arguments, so
+ * there is no key context. Points are rows of 32 bytes of device memory, [n][32], the row pointers
+ * 16-byte aligned: bit 255 of a row is ignored, values of p and above are accepted, the result is
+ * fully reduced, and a low-order point gives 32 zero bytes without an error. n == 0 is a no-op;
+ * n < 0, a null buffer with n > 0 and a misaligned row pointer are INVALID_ARGUMENT before any HIP
+ * call. Stream-ordered, no host synchronisation. */
+/* out[i] = X25519(scalar, u[i]); out may be u. */
+int efl_x25519(const uint8_t scalar[32], const uint8_t* u, uint8_t* out, int64_t n, void* stream);
+/* out[i] = X25519(scalar, sha256(prefix || string i)), the digest's 32 bytes in digest order (not
+ * efl_sha256_fdh's number form), for n byte strings packed as efl_sha256_fdh takes them. `prefix` is
+ * HOST memory of prefix_len bytes, 0 <= prefix_len <= 64 (the reference's is "curve25519"). Two
+ * launches: the hash writes out, the ladder runs over it in place. */
+int efl_x25519_hash(const uint8_t scalar[32], const char* prefix, int prefix_len, const char* chars,
+                    const int64_t* offsets, uint8_t* out, int64_t n, void* stream);
+
 /* ---- Key generation, HOST memory (GeneratePaillierKeypairOp, paillier.cc:833-904) ------------
  * The reference's keygen is a CPU op over GMP (mpz_probab_prime_p in find_prime, :851-863;
  * mpz_powm for hs, :884-888). These two are its arithmetic, on host buffers of little-endian
