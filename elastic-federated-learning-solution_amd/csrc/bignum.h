@@ -61,7 +61,9 @@ struct Uniform {
   __device__ __forceinline__ uint32_t operator()(int i) const { return p[i]; }
 };
 
-// a <- a * b * 2^(-32L) mod m, for a, b < m.
+// a <- a * b * 2^(-32L) mod m, for a, b < m. Operands from a peer may be anything below R = 2^(32L):
+// the result is then congruent and below R (t < R + m before the one subtraction), and below m
+// as soon as ONE operand is (t < 2m) — which the product by R^2 mod m that every op applies is.
 template <int L, class B>
 __device__ __forceinline__ void mont_mul(uint32_t (&a)[L], const B& b, const uint32_t* __restrict__ m,
                                          uint32_t minv) {

@@ -230,7 +230,8 @@ __device__ __forceinline__ void add_product(uint32_t (&z)[2 * L + 1], const uint
   }
 }
 
-// CRT join (efl_pl_crt_join): z = q^2 yp + p^2 yq mod n^2 for yp < p^2, yq < q^2 ([N][LN] words,
+// CRT join (efl_pl_crt_join): z = q^2 yp + p^2 yq mod n^2 for yp < p^2, yq < q^2 (exact while the sum
+// stays below 2 n^2, include/efl_hip.h: the one entry point that is not total) ([N][LN] words,
 // LN = the key's ln; z [N][2 LN]). With yp = x (q^2)^-1 mod p^2 and yq = x (p^2)^-1 mod q^2, z is x
 // mod n^2 (z = x mod p^2 and mod q^2). The key owner's encryption gets yp and yq straight from the
 // fixed-base walks mod p^2 and mod q^2, whose accumulators start from (q^2)^-1 and (p^2)^-1 instead
@@ -971,6 +972,8 @@ __global__ __launch_bounds__(256) void k_hex_write(const uint32_t* __restrict__ 
 
 // parse [-]hexdigits into L limbs; bad <- smallest index of a malformed / too-wide string.
 // Lane w assembles limbs w, w + 64, ... from their 8 digits; digits past 8 L must be '0'.
+// Without `neg` the caller keeps no sign (a ciphertext operand), so a text that starts with '-' is
+// bad too unless its magnitude is 0: the sign is never dropped.
 __global__ __launch_bounds__(256) void k_hex_parse(const char* __restrict__ chars,
                                                    const long long* __restrict__ offs, int L,
                                                    uint32_t* __restrict__ limbs,
@@ -989,6 +992,7 @@ __global__ __launch_bounds__(256) void k_hex_parse(const char* __restrict__ char
   }
   const long long nd = ok ? e - s : 0;
   uint32_t* x = limbs + i * L;
+  uint32_t any = 0;
   for (int w = lane; w < L; w += 64) {
     uint32_t acc = 0;
 #pragma unroll
@@ -1001,7 +1005,9 @@ __global__ __launch_bounds__(256) void k_hex_parse(const char* __restrict__ char
       }
     }
     x[w] = acc;
+    any |= acc;
   }
+  if (ng && !neg) ok = ok && any == 0u;
   for (long long d = 8ll * L + lane; d < nd; d += 64) ok = ok && chars[e - 1 - d] == '0';
   if (neg && lane == 0) neg[i] = ng ? 1 : 0;
   // one report per element: any lane that saw a bad character

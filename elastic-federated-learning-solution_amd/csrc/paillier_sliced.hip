@@ -1249,7 +1249,8 @@ __global__ __launch_bounds__(kSlBlock, C >= 32 ? EFL_MAT_WAVES32 : EFL_MAT_WAVES
     if (sgn ? started1 : started0) {
       from_lds<C28>(t, ACC[sgn], E, g);
       lds_sync();
-      store_from_mont28<C, G>(out[sgn], t, m28, minv28, ACC[sgn], E, g);   // the product's LDS is the scratch
+      // the product's LDS is the scratch; a product of 0 mod n^2 (x = n, y = 2) is written as 0
+      store_from_mont28<C, G>(out[sgn], t, m28, minv28, ACC[sgn], E, g, k.at(k.d.off_n2));
     } else {
       uint32_t one[C];
 #pragma unroll
@@ -1288,7 +1289,7 @@ __global__ __launch_bounds__(kSlBlock, C >= 32 ? 2 : EFL_DEC_WAVES) void k_matco
     s28::mont_mul<C28, G>(t, LdsElem{B, E}, m28, minv28, g);
   }
   lds_sync();
-  store_from_mont28<C, G>((sgn ? zneg : zpos) + o * L, t, m28, minv28, B, E, g);
+  store_from_mont28<C, G>((sgn ? zneg : zpos) + o * L, t, m28, minv28, B, E, g, k.at(k.d.off_n2));
 }
 
 // PaillierMatmul core, one group per output (see paillier.hip k_matmul)

@@ -162,6 +162,15 @@ int efl_fxp_decode_batched(const int64_t* const* mantissas, const int64_t* const
  *   off_hp       hp * R'' mod p with R'' = 2^(32*ln/2), hp = h-function (paillier.cc:28-37)
  *   off_qinvp    (q^-1 mod p) * R'' mod p
  *   off_max      ceil(2n/3) (paillier.cc:76-77), ln limbs
+ *
+ * Operands. A ciphertext operand row (x, y, hsa, the ciphertext of efl_pl_decrypt, the x rows of
+ * efl_pl_matmul) may hold ANY value below 2^(32*2*ln): it is taken mod n^2, as the reference's
+ * mpz_mul / mpz_mod / mpz_powm / mpz_invert take any integer — non-units (0, n, multiples of p or
+ * q), values at or above n^2, and, for a key that runs zero-padded in a larger class, values
+ * hundreds of bits above the modulus. Every result row is fully reduced (< n^2); a residue of 0 is
+ * written as 0, never as n^2. Only units have an inverse (efl_pl_invert, a negative scalar), and
+ * decryption is defined for units. The one exception is efl_pl_crt_join, which is not an op of the
+ * reference: its rows come from the library's own walks and carry the precondition stated there.
  */
 typedef struct {
   int32_t ln;
@@ -239,7 +248,11 @@ int efl_pl_fbpowm(const void* key_block, const efl_pl_key* key, const uint32_t* 
  * (1 + |m| n)^(sign) hsa mod n^2, the PaillierEncrypt ciphertext, with one Montgomery product. The
  * efl package gets yp and yq from efl_pl_fbpowm under the keys (p, hs mod p^2) and (q, hs mod q^2)
  * whose walks start from R (q^2)^-1 and R (p^2)^-1: the same ciphertexts, bit for bit, from
- * half-length products. ABORTED without the private key. */
+ * half-length products. ABORTED without the private key.
+ * Precondition: the join is two plain products, the sum s = q^2 yp + p^2 yq and ONE conditional
+ * subtraction of n^2, so v = s mod n^2 exactly when s < 2 n^2 — always for yp < p^2, yq < q^2, and
+ * for rows at or above p^2 / q^2 only while s stays below 2 n^2; past that v = s - n^2 mod 2^(64*ln).
+ * The library itself only feeds it walk results, which are reduced. */
 int efl_pl_crt_join(const void* key_block, const efl_pl_key* key, const uint32_t* yp, const uint32_t* yq,
                     const int64_t* plaintext, uint32_t* z, int64_t n, void* stream);
 
@@ -449,7 +462,11 @@ int efl_hex_lengths(const uint32_t* limbs, int limbs_per_elem, const int8_t* neg
                     int64_t* lengths, int64_t n, void* stream);
 int efl_hex_write(const uint32_t* limbs, int limbs_per_elem, const int8_t* negative,
                   const int64_t* offsets, char* chars, int64_t n, void* stream);
-/* mpz_set_str(..., 16) of n texts "[-]hexdigits" into limbs; bad <- -1 or the first bad index. */
+/* mpz_set_str(..., 16) of n texts "[-]hexdigits" (either case, any number of leading zeros) into
+ * limbs and sign bytes (1 = the text starts with '-'); bad <- -1 or the smallest bad index: an empty
+ * text, a character that is no hex digit, or a magnitude of more than 32*limbs_per_elem bits. With
+ * negative == NULL the caller keeps no sign (a ciphertext operand): a text that starts with '-' is
+ * then bad as well unless its magnitude is 0 — the sign is never dropped. */
 int efl_hex_parse(const char* chars, const int64_t* offsets, int limbs_per_elem, uint32_t* limbs,
                   int8_t* negative, int64_t n, int64_t* bad, void* stream);
 /* PaillierDecrypt<int64> output: mpz_get_sll (gmp_utils.cc:38-45): low 64 bits of |m|, signed. */

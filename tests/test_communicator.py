@@ -179,7 +179,8 @@ def _oracle_codec():
         return torch.from_numpy(M), torch.from_numpy(E)
 
     def dec(M, E, dtype=torch.float32):
-        return torch.from_numpy(fxp.decode(M.numpy(), E.numpy(), np.float32))
+        # with a GPU in the machine the communicator hands the received tensors over on the device
+        return torch.from_numpy(fxp.decode(M.cpu().numpy(), E.cpu().numpy(), np.float32))
     return enc, dec
 
 

@@ -110,3 +110,72 @@ def test_matmul_matches_the_oracle(keys):
     dec = owner.decrypt(zm, dtype="string").to_ints()
     assert dec == [sum(int(m[i, j]) * int(ym[j, q]) * 2 ** int(xe[i, j] + ye[j, q] - oe[i][q]) for j in range(v))
                    for i in range(u) for q in range(w)]
+
+
+def test_operand_domain(keys, efl):
+    """The whole operand domain (tests/operand_domain.py) through the default families: in a padded
+    class an operand may be hundreds of bits above the modulus (a 768-bit key's n^2 is 2^512 below
+    its 2048-bit rows), which the valid ciphertexts of the tests above never are. add, mul_scalar
+    (non-negative over the list, negative over the units), mul_exp2, invert, decrypt and a 2 x 3 x 2
+    matmul against the oracle, bit for bit."""
+    from operand_domain import first_mismatch, operands, rotate, tile
+    owner, public, okp = keys
+    key = public.key
+    HT = efl.HexTensor
+    M, T = okp.n2, 1 << (32 * key.lc)
+    ops = operands(okp.n, okp.p, okp.q, key.lc)
+    padded = T // M >= 1 << 32
+    assert padded == (key.ln != 256)                 # every size of this module but the 8192-bit one
+    if padded:
+        assert sum(o.x > M << 32 for o in ops) >= 4
+    count = len(ops) if key.ln == 256 else 70 if key.ln < 128 else 24       # the 8192-bit key: untiled
+    xs = [o.x for o in tile(ops, count)]
+    units = [o for o in ops if o.unit]
+    us = [o.x for o in tile(units, count)]
+
+    def check(got, want, labels, what):
+        msg = first_mismatch(got, want, labels)
+        assert not msg, f"{what}: {msg}"
+
+    for r in (0, 1, 5, 11):
+        ys = tile(rotate([o.x for o in ops], r), count)
+        check(public.add(HT.from_ints(xs), HT.from_ints(ys)).to_hex().to_ints(),
+              [P.add(okp, x, y) for x, y in zip(xs, ys)], ops, f"add, y rotated by {r}")
+    for y in (0, 1, 3, 2**40 + 1):
+        check(public.mul_scalar(HT.from_ints(xs), torch.tensor(y)).to_hex().to_ints(),
+              [P.mul_scalar(okp, x, y) for x in xs], ops, f"mul_scalar {y}")
+    for y in (-1, -7, -2**63):
+        check(public.mul_scalar(HT.from_ints(us), torch.tensor(y)).to_hex().to_ints(),
+              [P.mul_scalar(okp, x, y) for x in us], units, f"mul_scalar {y} over the units")
+    for y in (0, 1, 33):
+        check(public.mul_exp2(HT.from_ints(xs), torch.tensor(y)).to_hex().to_ints(),
+              [P.mul_exp2(okp, x, y) for x in xs], ops, f"mul_exp2 {y}")
+    check(public.invert(HT.from_ints(us)).to_hex().to_ints(), [P.invert(okp, x) for x in us], units, "invert")
+    by = {o.label: o.x for o in ops}
+    batch = list(us)
+    batch[5], batch[9] = by["M+n"], 0
+    with pytest.raises(efl.errors.InvalidArgumentError, match="element 5 has no inverse"):
+        public.invert(HT.from_ints(batch))
+    # decryption: the units, and a fresh ciphertext lifted by multiples of M up to T
+    c0 = public.encrypt(torch.tensor([-12345])).tensor.to_hex().to_ints()[0]
+    lifted = [c0 + j * M for j in {1, 2, (T - 1 - c0) // M} if j and c0 + j * M < T]
+    assert not padded or len(lifted) == 3
+    cs = [o.x for o in units] + lifted
+    got = owner.decrypt(HT.from_ints(cs)).strings()
+    want = [P.hx(P.decrypt(okp, x)) for x in cs]
+    assert got == want, next(i for i in range(len(cs)) if got[i] != want[i])
+    assert want[len(units):] == ["-3039"] * len(lifted)
+    # matmul: every class in some term with y >= 0 (a product of 0 mod n^2 among the outputs),
+    # the units with mixed signs
+    xe, ye = [[0, 2, 1], [3, 0, 5]], [[0, 1], [2, 0], [1, 3]]
+    zeros = 0
+    for vals, ym in ([o.x for o in ops], [[2, 1], [0, 3], [0, 1]]), ([o.x for o in units], [[3, -2], [-1, 0], [5, -7]]):
+        for i in range(0, len(vals), 6):
+            xm = [[vals[(i + j) % len(vals)] for j in range(3)], [vals[(i + 3 + j) % len(vals)] for j in range(3)]]
+            zm, ze = public.matmul(HT.from_ints([v for row in xm for v in row], (2, 3)), torch.tensor(xe),
+                                   torch.tensor(ym), torch.tensor(ye))
+            wm, we = P.matmul(okp, xm, xe, ym, ye)
+            assert ze.cpu().tolist() == we
+            assert zm.to_hex().strings() == [P.hx(v) for row in wm for v in row], (i, ym)
+            zeros += sum(v == 0 for row in wm for v in row)
+    assert zeros >= 2
