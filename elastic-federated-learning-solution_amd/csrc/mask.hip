@@ -24,6 +24,7 @@
 #include "common.h"
 #include "pl_common.h"
 #include "box_muller_math.h"
+#include "group_div.h"
 #include "sincos_angle.h"
 
 // Every product and sum rounds on its own, as TF's separate ops (and numpy in the oracle) do:
@@ -80,14 +81,8 @@ __device__ __forceinline__ float noise(float u, float x, float d) {
   else return n;
 }
 
-// Division of a lane-group index by the row length: q = g / d for g < 2^31 as one 64-bit product and
-// a shift (Granlund-Montgomery: l = ceil(log2 d), m = floor(2^(31 + l) / d) + 1 < 2^32 is exact for
-// every g < 2^31), from the magic (m, 31 + l) the host passes; m == 0 (more than 2^31 groups) takes
-// the 64-bit division.
-__device__ __forceinline__ long long div_groups(long long g, long long d, uint32_t m, int sh) {
-  if (m) return (long long)(((uint64_t)(uint32_t)g * m) >> sh);
-  return g / d;
-}
+// Division of a lane-group index by the row length, div_groups(g, d, m, sh) with the magic (m, sh)
+// of group_magic(total, d): group_div.h (swept on the host by tests/test_group_div_host.py).
 
 // op 0: o0 = n            (generate_suitable_noise)
 // op 1: o0 = n, o1 = x-n  (share: the sent share and the kept one)
@@ -515,16 +510,6 @@ bool lanes_ok(long long lanes) { return lanes / kBlock < (1ll << 31); }
 #define EFL_K_NOISE2D1(NB, ST) k_noise<2, 1, NB, ST>
 #define EFL_K_NOISE2D2(NB, ST) k_noise<2, 2, NB, ST>
 
-// the magic (m, shift) of div_groups for d, or m = 0 when the groups pass 2^31
-void group_magic(long long total, long long d, uint32_t* m, int* sh) {
-  *m = 0;
-  *sh = 0;
-  if (total <= 0 || total >= (1ll << 31) || d <= 0) return;
-  int l = 0;
-  while ((1ll << l) < d) ++l;
-  *m = (uint32_t)(((1ull << (31 + l)) / (unsigned long long)d) + 1ull);
-  *sh = 31 + l;
-}
 // share / weight noise (op 1 / 2) with the two outputs over the two halves of a wave
 // (efl_fxp_tune(30, 1), the default since round 6): lanes l and l + 32 load the same 16-byte group
 // (one HBM read; the second half's request hits the line the first fetched), draw the same Philox

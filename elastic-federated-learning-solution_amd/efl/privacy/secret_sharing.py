@@ -42,7 +42,7 @@ class NoiseStream:
     def reset(self, seed: int | None = None, counter: int = 0):
         with self._lock:
             self.seed = int.from_bytes(os.urandom(8), "little") if seed is None else int(seed) & (2**64 - 1)
-            self.counter = int(counter)
+            self.counter = int(counter) & (2**64 - 1)
 
     def take(self, n: int) -> tuple[int, int]:
         """(seed, ctr0) for a call over n elements; advances the counter by ceil(n / 4)."""
