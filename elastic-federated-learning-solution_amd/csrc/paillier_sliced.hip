@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "pl_common.h"
+#include "powm28.h"
 #include "sliced.h"
 #include "sliced28.h"
 
@@ -22,6 +23,9 @@ namespace pl {
 namespace {
 
 using namespace sl;
+using s28::load28;
+using s28::pad4;
+using s28::store28;
 
 constexpr int kSlBlock = 64;
 
@@ -30,12 +34,6 @@ template <int C>
 __device__ __forceinline__ void slice_prefix(uint32_t (&x)[C], const uint32_t* __restrict__ p, int len, int g) {
 #pragma unroll
   for (int j = 0; j < C; ++j) x[j] = g * C + j < len ? p[g * C + j] : 0u;
-}
-
-template <int C>
-__device__ __forceinline__ void from_lds(uint32_t (&x)[C], const uint32_t* base, int E, int g) {
-#pragma unroll
-  for (int j = 0; j < C; ++j) x[j] = base[(g * C + j) * E];
 }
 
 // the element's a (Philox stream, as paillier.hip's draw_a) into LDS; Philox blocks split over the group
@@ -654,19 +652,6 @@ __global__ __launch_bounds__(kSlBlock, C >= 32 ? 2 : EFL_DEC_WAVES) void k_fxp_a
 // of y), so the groups of a wave share every term's |y| and differ only through d; they also have
 // the same number of multiplies (sum of popcount(|y|)), so their event lists are about equally long.
 
-// padded radix-2^28 slice of one element in HBM: lane g's C28 limbs at [g * CP, g * CP + C28)
-template <int C28>
-constexpr int pad4() { return (C28 + 3) & ~3; }
-
-template <int C28>
-__device__ __forceinline__ void store28(uint32_t* __restrict__ q, const uint32_t (&t)[C28]) {
-  constexpr int CP = pad4<C28>();
-#pragma unroll
-  for (int j = 0; j < CP; j += 4)
-    *reinterpret_cast<uint4*>(q + j) = make_uint4(t[j], j + 1 < C28 ? t[j + 1] : 0u, j + 2 < C28 ? t[j + 2] : 0u,
-                                                  j + 3 < C28 ? t[j + 3] : 0u);
-}
-
 // Windowed terms (round 2): every term's exponent |y| is cut right to left into windows of up to
 // kMatWin bits that start at a 1 bit (a window (s, v): bits s .. s + kMatWin - 1 of |y|, v odd), so
 // x^|y| = prod over its windows of (x^v)^(2^s). Each x element gets its odd powers x, x^3, ...,
@@ -846,19 +831,6 @@ __global__ __launch_bounds__(kSlBlock, C >= 32 ? 2 : EFL_DEC_WAVES) void k_tomon
   for (int e2 = 1; e2 < kMatEntries; ++e2) {
     s28::mont_mul<C28, G>(t, LdsElem{B, E}, m28, minv28, g);
     store28<C28>(q + (long long)e2 * estride, t);
-  }
-}
-
-template <int C28>
-__device__ __forceinline__ void load28(uint32_t (&t)[C28], const uint32_t* __restrict__ q) {
-  constexpr int CP = pad4<C28>();
-#pragma unroll
-  for (int j = 0; j < CP; j += 4) {
-    const uint4 v = *reinterpret_cast<const uint4*>(q + j);
-    t[j] = v.x;
-    if (j + 1 < C28) t[j + 1] = v.y;
-    if (j + 2 < C28) t[j + 2] = v.z;
-    if (j + 3 < C28) t[j + 3] = v.w;
   }
 }
 
@@ -1354,16 +1326,11 @@ __global__ __launch_bounds__(kSlBlock) SL_OCC void k_matmul(Key k, const uint32_
 // decryption: L = ln limbs (x^2 for x = p, q), half slices of C/2 limbs for numbers mod x
 // ------------------------------------------------------------------------------------------
 
-// Sliding-window exponentiation by the decryption exponent x - 1 (the same for every element, so
-// the window walk is wave-uniform): the element's odd powers c^1, c^3, ..., c^(2^kDecWin - 1) in
-// radix-2^28 Montgomery form go to a global scratch slab (kDecEntries x G x CP words per element,
-// this lane's CP-word slice at +g*CP), and every multiply stages its entry in LDS. Products per
-// modulus: bits(x-1) - 1 squarings + ~bits/(kDecWin+1) multiplies + 2^(kDecWin-1) for the table,
-// against bits - 1 + popcount - 1 for the binary method: 2404 instead of ~3071 at 4096-bit n.
-constexpr int kDecWin = 5, kDecEntries = 1 << (kDecWin - 1);
-
-// bit b of the uniform exponent
-__device__ __forceinline__ uint32_t ebit(const uint32_t* ex, int b) { return (ex[b >> 5] >> (b & 31)) & 1u; }
+// Sliding-window exponentiation by the decryption exponent x - 1 (csrc/powm28.h): the window width,
+// and the odd powers c^1, c^3, ..., c^(2^kDecWin - 1) each element keeps in its global scratch slab
+// (kDecEntries x G x CP words, this lane's CP-word slice at +g*CP)
+constexpr int kDecWin = s28::kWin, kDecEntries = 1 << (kDecWin - 1);
+static_assert(kDecEntries == s28::kEntries, "the slab holds the walk's table");
 
 // res = L_x(c^(x-1) mod x^2) * h mod x   (paillier.cc:28-48). tab: this element's odd-power slab
 // (sliding window), or null for the binary method.
@@ -1399,250 +1366,28 @@ __device__ __forceinline__ void m_func(uint32_t (&res)[C / 2], const uint32_t* _
   // keep the key constants the code after the exponentiation needs from being loaded (and held
   // in VGPRs) across it: the loop wants its registers for the accumulators
   asm volatile("" ::: "memory");
-  // the running value's limb layout: folded (symmetric squarings, sliced28.h) for the 32-word-slice
-  // families over G >= 2 lanes (the 2048- to 8192-bit keys' defaults, 37-limb slices), blocked
-  // otherwise (the short-slice families keep CIOS: their unrolled folded loops cost compile time
-  // for little)
-  constexpr bool kFold = G > 1 && C == 32 && EFL_SQR_FOLD;
   // SOS squarings for the 37-limb slices over 2 or 4 lanes (the 2048- and 4096-bit keys' defaults)
-  // when the sliding window's table slab is there (the binary method keeps CIOS)
-  constexpr bool kSos = !kFold && (G == 2 || G == 4) && C == 32 && EFL_SQR_SOS;
+  // when the sliding window's table slab is there; every other family, and the binary method
+  // (efl_pl_tune(ln, 2, 0)), squares by CIOS
+  constexpr bool kSos = (G == 2 || G == 4) && C == 32 && EFL_SQR_SOS;
   const uint32_t minv28 = second ? k.d.q2_minv28 : k.d.p2_minv28;
-  const uint32_t* r2_28 = k.at(second ? k.d.off_q2_r2_28[kLog2G] : k.d.off_p2_r2_28[kLog2G]);
-  const uint32_t* m28_at = k.at(second ? k.d.off_q2_28 : k.d.off_p2_28);
-  if constexpr (kFold) {
-    uint32_t a[C28], m28[C28];
-    s28::from_words_folded<C28, G>(a, SCR, E, L, g);
-    s28::slice_uniform_folded<C28, G>(m28, m28_at, g);
-    s28::mont_mul_folded<C28, G>(a, Uniform{r2_28}, BASE, E, m28, minv28, g);   // c R28
-    lds_sync();
-    if (tab) {
-      constexpr int CP = pad4<C28>();
-      uint32_t* slot = tab + g * CP;               // entry e at slot + e * G * CP (folded slices)
-      store28<C28>(slot, a);
-      uint32_t c2[C28];
-#pragma unroll
-      for (int j = 0; j < C28; ++j) c2[j] = a[j];
-      s28::fold_mont<C28, G>(c2, SCR, E, m28, minv28, g, true);
-      lds_sync();
-      s28::to_lds_folded<C28, G>(BASE, E, g, c2);
-      lds_sync();
-#pragma unroll 1
-      for (int e2 = 1; e2 < kDecEntries; ++e2) {
-        s28::fold_mont<C28, G>(a, BASE, E, m28, minv28, g, false);
-        store28<C28>(slot + (size_t)e2 * G * CP, a);
-      }
-      lds_sync();
-      int b = ebits - 1;
-      int j = b - kDecWin + 1 > 0 ? b - kDecWin + 1 : 0;
-      while (!ebit(ex, j)) ++j;
-      uint32_t v = 0;
-      for (int t = b; t >= j; --t) v = (v << 1) | ebit(ex, t);
-      load28<C28>(a, slot + (size_t)(v >> 1) * G * CP);
-      b = j - 1;
-      // The window walk with one fold_mont call site for its squarings and multiplies alike: the
-      // next operation is planned at the top of the loop (a lone squaring for a 0 bit, or a window's
-      // squarings, then its multiply). The entry is loaded just before its multiply, not held in
-      // VGPRs across the squarings (the squaring needs them; the other wave on the SIMD covers the
-      // load, once per window)
-      size_t ent_at = 0;
-      int sq_left = 0;
-      bool mul_next = false;
-#pragma unroll 1
-      for (;;) {
-        if (sq_left == 0 && !mul_next) {
-          if (b < 0) break;
-          if (!ebit(ex, b)) {
-            sq_left = 1;
-            --b;
-          } else {
-            j = b - kDecWin + 1 > 0 ? b - kDecWin + 1 : 0;
-            while (!ebit(ex, j)) ++j;
-            v = 0;
-            for (int t = b; t >= j; --t) v = (v << 1) | ebit(ex, t);
-            ent_at = (size_t)(v >> 1) * G * CP;
-            sq_left = b - j + 1;
-            mul_next = true;
-            b = j - 1;
-          }
-        }
-        const bool sq = sq_left > 0;
-        if (!sq) {
-          uint32_t ent[C28];
-          load28<C28>(ent, slot + ent_at);
-          s28::to_lds_folded<C28, G>(BASE, E, g, ent);
-          lds_sync();
-        }
-        s28::fold_mont<C28, G>(a, sq ? SCR : BASE, E, m28, minv28, g, sq);
-        lds_sync();
-        if (sq) --sq_left;
-        else mul_next = false;
-      }
-    } else {
-      s28::to_lds_folded<C28, G>(BASE, E, g, a);
-      lds_sync();
-#pragma unroll 1
-      for (int b = ebits - 2; b >= 0; --b) {
-        s28::fold_mont<C28, G>(a, SCR, E, m28, minv28, g, true);
-        lds_sync();
-        if (ebit(ex, b)) {
-          s28::fold_mont<C28, G>(a, BASE, E, m28, minv28, g, false);
-          lds_sync();
-        }
-      }
-    }
-    s28::mont_mul_folded<C28, G>(a, Unit{}, BASE, E, m28, minv28, g);   // y = c^(x-1) mod x^2
-    lds_sync();
-    s28::to_lds_folded<C28, G>(SCR, E, g, a);
-    lds_sync();
-  } else if constexpr (kSos) {
-    // the SOS squarings (sliced28.h sos_sqr) take both LDS arrays as the square's 2 L words; one
-    // call site for every squaring of the window walk (its code is about 3,500 instructions)
-    uint32_t a[C28], m28[C28];
-    s28::from_words<C28>(a, SCR, E, L, g);
-    slice_uniform<C28>(m28, m28_at, g);
-    s28::mont_mul<C28, G>(a, Uniform{r2_28}, m28, minv28, g);
-    lds_sync();
-    if (!tab) {                                    // the binary method (efl_pl_tune(ln, 2, 0)): CIOS
-      to_lds<C28>(BASE, E, g, a);
-#pragma unroll 1
-      for (int b = ebits - 2; b >= 0; --b) {
-        s28::mont_sqr<C28, G>(a, SCR, E, m28, minv28, g);
-        if (ebit(ex, b)) s28::mont_mul<C28, G>(a, LdsElem{BASE, E}, m28, minv28, g);
-      }
-    } else {
-    constexpr int CP = pad4<C28>();
-    uint32_t* slot = tab + g * CP;                 // entry e at slot + e * G * CP
-    store28<C28>(slot, a);
-    int b = ebits - 1;
-    int j = b - kDecWin + 1 > 0 ? b - kDecWin + 1 : 0;
-    while (!ebit(ex, j)) ++j;
-    uint32_t v = 0;
-    for (int t = b; t >= j; --t) v = (v << 1) | ebit(ex, t);
-    // phase -1: c^2, then the odd powers; phase 0: the window walk
-    int nsq = 1;
-    int e2 = 0;                                    // table entries built so far (after c^2)
-    bool build = true;
-    size_t ent_at = 0;
-    bool mul = false;
-#pragma unroll 1
-    for (;;) {
-#pragma unroll 1
-      for (int t = 0; t < nsq; ++t) {
-        s28::sos_sqr<C28, G>(a, BASE, E, m28, minv28, g);
-        lds_sync();
-      }
-      if (build) {
-        // a = c^2: stage it, then T[e] = T[e-1] c^2 from c
-        to_lds<C28>(BASE, E, g, a);
-        lds_sync();
-        load28<C28>(a, slot);
-#pragma unroll 1
-        for (e2 = 1; e2 < kDecEntries; ++e2) {
-          s28::mont_mul<C28, G>(a, LdsElem{BASE, E}, m28, minv28, g);
-          store28<C28>(slot + (size_t)e2 * G * CP, a);
-        }
-        lds_sync();
-        load28<C28>(a, slot + (size_t)(v >> 1) * G * CP);
-        b = j - 1;
-        build = false;
-      } else if (mul) {
-        uint32_t ent[C28];
-        load28<C28>(ent, slot + ent_at);
-        to_lds<C28>(BASE, E, g, ent);
-        lds_sync();
-        s28::mont_mul<C28, G>(a, LdsElem{BASE, E}, m28, minv28, g);
-        lds_sync();
-      }
-      if (b < 0) break;
-      if (!ebit(ex, b)) {
-        nsq = 1;
-        mul = false;
-        --b;
-      } else {
-        j = b - kDecWin + 1 > 0 ? b - kDecWin + 1 : 0;
-        while (!ebit(ex, j)) ++j;
-        v = 0;
-        for (int t = b; t >= j; --t) v = (v << 1) | ebit(ex, t);
-        ent_at = (size_t)(v >> 1) * G * CP;
-        nsq = b - j + 1;
-        mul = true;
-        b = j - 1;
-      }
-    }
-    }
-    s28::mont_mul<C28, G>(a, Unit{}, m28, minv28, g);   // y = c^(x-1) mod x^2
-    lds_sync();
-    to_lds<C28>(SCR, E, g, a);
-    lds_sync();
-  } else {
   uint32_t a[C28], m28[C28];
   s28::from_words<C28>(a, SCR, E, L, g);
-  slice_uniform<C28>(m28, m28_at, g);
-  s28::mont_mul<C28, G>(a, Uniform{r2_28}, m28, minv28, g);
+  slice_uniform<C28>(m28, k.at(second ? k.d.off_q2_28 : k.d.off_p2_28), g);
+  s28::mont_mul<C28, G>(a, Uniform{k.at(second ? k.d.off_q2_r2_28[kLog2G] : k.d.off_p2_r2_28[kLog2G])}, m28, minv28,
+                        g);   // c R28
   lds_sync();
-  if (tab) {
-    constexpr int CP = pad4<C28>();
-    uint32_t* slot = tab + g * CP;                 // entry e at slot + e * G * CP
-    // odd powers: T[0] = c, T[e] = T[e-1] c^2
-    store28<C28>(slot, a);
-    uint32_t c2[C28];
-#pragma unroll
-    for (int j = 0; j < C28; ++j) c2[j] = a[j];
-    s28::mont_sqr<C28, G>(c2, SCR, E, m28, minv28, g);
-    lds_sync();
-    to_lds<C28>(BASE, E, g, c2);
-    lds_sync();
-#pragma unroll 1
-    for (int e2 = 1; e2 < kDecEntries; ++e2) {
-      s28::mont_mul<C28, G>(a, LdsElem{BASE, E}, m28, minv28, g);
-      store28<C28>(slot + (size_t)e2 * G * CP, a);
-    }
-    lds_sync();
-    // left to right: windows of up to kDecWin bits that end in a 1 bit (the top bit is 1)
-    int b = ebits - 1;
-    int j = b - kDecWin + 1 > 0 ? b - kDecWin + 1 : 0;
-    while (!ebit(ex, j)) ++j;
-    uint32_t v = 0;
-    for (int t = b; t >= j; --t) v = (v << 1) | ebit(ex, t);
-    load28<C28>(a, slot + (size_t)(v >> 1) * G * CP);
-    b = j - 1;
-#pragma unroll 1
-    while (b >= 0) {
-      if (!ebit(ex, b)) {
-        s28::mont_sqr<C28, G>(a, SCR, E, m28, minv28, g);
-        --b;
-        continue;
-      }
-      j = b - kDecWin + 1 > 0 ? b - kDecWin + 1 : 0;
-      while (!ebit(ex, j)) ++j;
-      v = 0;
-      for (int t = b; t >= j; --t) v = (v << 1) | ebit(ex, t);
-      uint32_t ent[C28];
-      load28<C28>(ent, slot + (size_t)(v >> 1) * G * CP);   // in flight during the squarings
-#pragma unroll 1
-      for (int t = b; t >= j; --t) s28::mont_sqr<C28, G>(a, SCR, E, m28, minv28, g);
-      // (mul_fips1 here, for one-lane numbers, measured 3 % slower: the 1024-bit decryption's 256
-      // VGPRs were already full, round 4)
-      to_lds<C28>(BASE, E, g, ent);
-      lds_sync();
-      s28::mont_mul<C28, G>(a, LdsElem{BASE, E}, m28, minv28, g);
-      lds_sync();
-      b = j - 1;
-    }
+  if (!tab) {
+    s28::powm_binary<C28, G>(a, ex, ebits, BASE, SCR, E, m28, minv28, g);
   } else {
-    to_lds<C28>(BASE, E, g, a);
-#pragma unroll 1
-    for (int b = ebits - 2; b >= 0; --b) {
-      s28::mont_sqr<C28, G>(a, SCR, E, m28, minv28, g);
-      if (ebit(ex, b)) s28::mont_mul<C28, G>(a, LdsElem{BASE, E}, m28, minv28, g);
-    }
+    uint32_t* slot = tab + g * pad4<C28>();        // this lane's slice of the slab's entries
+    if constexpr (kSos) s28::powm_window<C28, G, true>(a, slot, ex, ebits, BASE, SCR, E, m28, minv28, g);
+    else s28::powm_window_preload<C28, G>(a, slot, ex, ebits, BASE, SCR, E, m28, minv28, g);
   }
   s28::mont_mul<C28, G>(a, Unit{}, m28, minv28, g);   // y = c^(x-1) mod x^2 (< x^2; y = 1 mod x, so y >= 1)
   lds_sync();
   to_lds<C28>(SCR, E, g, a);
   lds_sync();
-  }
   s28::to_words<C>(t, SCR, E, L28, g);
   lds_sync();
   asm volatile("" ::: "memory");
@@ -1650,7 +1395,9 @@ __device__ __forceinline__ void m_func(uint32_t (&res)[C / 2], const uint32_t* _
   to_lds<C>(SCR, E, g, t);
   lds_sync();
   // (y - 1) / x exactly = (y - 1) * x^-1 mod 2^(32 LH): operand scanning, limb ii of the
-  // quotient leaves lane 0 after step ii
+  // quotient leaves lane 0 after step ii. (sl::scan_mul_add's loop from zero, without its high half.
+  // It stays written out: through the shared helper k_decrypt<32, 8> was allocated differently, 608
+  // spilled dwords instead of 553, and ran 1.4 % slower)
   uint32_t xi[CH], q[CH];
   slice_uniform<CH>(xi, k.at(second ? k.d.off_qinv_w : k.d.off_pinv_w), g);
 #pragma unroll
@@ -1689,7 +1436,7 @@ template <int C, int G>
 __global__ __launch_bounds__(kSlBlock, C >= 32 ? 2 : EFL_DEC_WAVES) void k_decrypt(Key k, const uint32_t* __restrict__ ct,
                                                       uint32_t* __restrict__ mag, signed char* __restrict__ neg,
                                                       long long N, uint32_t* __restrict__ win) {
-  constexpr int L = C * G, E = kSlBlock / G, CH = C / 2, LH = L / 2;
+  constexpr int L = C * G, E = kSlBlock / G, CH = C / 2;
   constexpr int L28 = s28::limbs_per_lane(L, G) * G;   // LDS arrays also hold radix-2^28 numbers
   extern __shared__ uint32_t lds[];
   SL_ELEMENT(E, G)
@@ -1724,30 +1471,7 @@ __global__ __launch_bounds__(kSlBlock, C >= 32 ? 2 : EFL_DEC_WAVES) void k_decry
   uint32_t t[CH];
 #pragma unroll
   for (int j = 0; j < CH; ++j) t[j] = mq[j];
-  uint32_t pend = 0;
-#pragma unroll 1
-  for (int ii = 0; ii < LH; ++ii) {
-    const uint32_t hv = BASE[ii * E];
-    uint32_t c1 = 0;
-#pragma unroll
-    for (int j = 0; j < CH; ++j) {
-      const uint64_t p = mad(qh[j], hv, (uint64_t)t[j] + c1);
-      t[j] = (uint32_t)p;
-      c1 = (uint32_t)(p >> 32);
-    }
-    if (g == 0) SCR[ii * E] = t[0];
-    uint32_t in = from_next<G>(t[0]);
-    if (g == G - 1) in = 0;
-#pragma unroll
-    for (int j = 0; j < CH - 1; ++j) t[j] = t[j + 1];
-    const uint64_t s = (uint64_t)in + pend + c1;
-    t[CH - 1] = (uint32_t)s;
-    pend = (uint32_t)(s >> 32);
-  }
-  resolve_carries<CH, G>(t, pend, g);
-#pragma unroll
-  for (int j = 0; j < CH; ++j) SCR[(LH + g * CH + j) * E] = t[j];
-  lds_sync();
+  scan_mul_add<CH, G>(t, qh, BASE, SCR, E, g);
   uint32_t mm[C], ref[C];
   from_lds<C>(mm, SCR, E, g);
   // signed: m > max (= ceil(2n/3)) -> m - n  (paillier.cc:308-310)

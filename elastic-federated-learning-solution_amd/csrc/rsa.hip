@@ -21,6 +21,7 @@
 // unblinding (rsaset.hip composes it with the batched inversion of paillier.hip).
 // k_sha256_fdh: FIPS 180-4 SHA-256 of n packed byte strings, one lane per string, the digest as the
 // low 8 words of a row.
+#include "powm28.h"
 #include "rsa.h"
 #include "sha256.h"
 #include "sliced.h"
@@ -31,117 +32,12 @@ namespace rsa {
 namespace {
 
 using namespace sl;
+using s28::kEntries;
+using s28::pad4;
 
 constexpr int kWave = 64;
-// window width and odd-power entries of the walk: the decryption's (paillier_sliced.hip kDecWin)
-constexpr int kWin = 5, kEntries = 1 << (kWin - 1);
 // elements per launch (the slab holds kEntries + 1 numbers for each)
 constexpr long long kChunk = 1 << 18;
-
-template <int C28>
-constexpr int pad4() { return (C28 + 3) & ~3; }
-
-template <int C28>
-__device__ __forceinline__ void store28(uint32_t* q, const uint32_t (&t)[C28]) {
-  constexpr int CP = pad4<C28>();
-#pragma unroll
-  for (int j = 0; j < CP; j += 4)
-    *reinterpret_cast<uint4*>(q + j) = make_uint4(t[j], j + 1 < C28 ? t[j + 1] : 0u, j + 2 < C28 ? t[j + 2] : 0u,
-                                                  j + 3 < C28 ? t[j + 3] : 0u);
-}
-template <int C28>
-__device__ __forceinline__ void load28(uint32_t (&t)[C28], const uint32_t* q) {
-  constexpr int CP = pad4<C28>();
-#pragma unroll
-  for (int j = 0; j < CP; j += 4) {
-    const uint4 v = *reinterpret_cast<const uint4*>(q + j);
-    t[j] = v.x;
-    if (j + 1 < C28) t[j + 1] = v.y;
-    if (j + 2 < C28) t[j + 2] = v.z;
-    if (j + 3 < C28) t[j + 3] = v.w;
-  }
-}
-
-template <int C>
-__device__ __forceinline__ void from_lds(uint32_t (&x)[C], const uint32_t* base, int E, int g) {
-#pragma unroll
-  for (int j = 0; j < C; ++j) x[j] = base[(g * C + j) * E];
-}
-
-// bit b of a wave-uniform exponent
-__device__ __forceinline__ uint32_t ebit(const uint32_t* ex, int b) { return (ex[b >> 5] >> (b & 31)) & 1u; }
-
-// one squaring with the method of the family; the SOS square takes both LDS arrays (contiguous)
-template <int C28, int G, bool SOS>
-__device__ __forceinline__ void sqr(uint32_t (&a)[C28], uint32_t* BASE, uint32_t* SCR, int E,
-                                    const uint32_t (&m28)[C28], uint32_t minv28, int g) {
-  if constexpr (SOS) s28::sos_sqr<C28, G>(a, BASE, E, m28, minv28, g);
-  else s28::mont_sqr<C28, G>(a, SCR, E, m28, minv28, g);
-  lds_sync();
-}
-
-// a <- a^ex in radix-2^28 Montgomery form (lazy: < 2m), ex of ebits >= 1 bits, uniform over the
-// wave. slot: this lane's slice of the element's slab (entry k at slot + k G CP). The loop has one
-// site for its squarings (the table's c^2, a 0 bit's lone squaring, a window's run): the next step is
-// planned at its end.
-template <int C28, int G, bool SOS>
-__device__ __forceinline__ void powm_window(uint32_t (&a)[C28], uint32_t* slot, const uint32_t* ex, int ebits,
-                                            uint32_t* BASE, uint32_t* SCR, int E, const uint32_t (&m28)[C28],
-                                            uint32_t minv28, int g) {
-  constexpr int CP = pad4<C28>();
-  store28<C28>(slot, a);
-  int b = ebits - 1;
-  int j = b - kWin + 1 > 0 ? b - kWin + 1 : 0;
-  while (!ebit(ex, j)) ++j;
-  uint32_t v = 0;
-  for (int t = b; t >= j; --t) v = (v << 1) | ebit(ex, t);
-  int nsq = 1;
-  bool build = true, mul = false;
-  size_t ent_at = 0;
-#pragma unroll 1
-  for (;;) {
-#pragma unroll 1
-    for (int t = 0; t < nsq; ++t) sqr<C28, G, SOS>(a, BASE, SCR, E, m28, minv28, g);
-    if (build) {
-      // a = c^2: stage it, then the odd powers T[k] = T[k-1] c^2 from T[0] = c
-      to_lds<C28>(BASE, E, g, a);
-      lds_sync();
-      load28<C28>(a, slot);
-#pragma unroll 1
-      for (int k = 1; k < kEntries; ++k) {
-        s28::mont_mul<C28, G>(a, LdsElem{BASE, E}, m28, minv28, g);
-        store28<C28>(slot + (size_t)k * G * CP, a);
-      }
-      lds_sync();
-      load28<C28>(a, slot + (size_t)(v >> 1) * G * CP);   // the top window
-      b = j - 1;
-      build = false;
-    } else if (mul) {
-      uint32_t ent[C28];
-      load28<C28>(ent, slot + ent_at);
-      to_lds<C28>(BASE, E, g, ent);
-      lds_sync();
-      s28::mont_mul<C28, G>(a, LdsElem{BASE, E}, m28, minv28, g);
-      lds_sync();
-    }
-    if (b < 0) break;
-    if (!ebit(ex, b)) {
-      nsq = 1;
-      mul = false;
-      --b;
-    } else {
-      // a window of up to kWin bits that ends in a 1 bit
-      j = b - kWin + 1 > 0 ? b - kWin + 1 : 0;
-      while (!ebit(ex, j)) ++j;
-      v = 0;
-      for (int t = b; t >= j; --t) v = (v << 1) | ebit(ex, t);
-      ent_at = (size_t)(v >> 1) * G * CP;
-      nsq = b - j + 1;
-      mul = true;
-      b = j - 1;
-    }
-  }
-}
 
 // C 32-bit words per lane of a number mod p (L = C G words); rows of x and s have k.W words, 2 L
 // (balanced primes) or L (p or q longer than half of N's class: the high half of x is absent)
@@ -199,8 +95,8 @@ __global__ __launch_bounds__(kWave, C >= 32 ? 2 : 4) void k_rsa_sign(Key k, cons
     lds_sync();
     s28::mont_mul<C28, G>(a, Uniform{k.at(second ? p1.off_r2_28 : p0.off_r2_28)}, m28, minv28, g);   // x R28
     lds_sync();
-    powm_window<C28, G, kSos>(a, slot, k.at(second ? p1.off_dx : p0.off_dx), second ? p1.dbits : p0.dbits, BASE,
-                              SCR, E, m28, minv28, g);
+    s28::powm_window<C28, G, kSos>(a, slot, k.at(second ? p1.off_dx : p0.off_dx), second ? p1.dbits : p0.dbits, BASE,
+                                   SCR, E, m28, minv28, g);
     s28::mont_mul<C28, G>(a, Unit{}, m28, minv28, g);   // x^dx mod m, fully reduced
     lds_sync();
     to_lds<C28>(SCR, E, g, a);
@@ -231,31 +127,7 @@ __global__ __launch_bounds__(kWave, C >= 32 ? 2 : 4) void k_rsa_sign(Key k, cons
   slice_uniform<C>(qh, k.at(k.pr[1].off_x), g);
 #pragma unroll
   for (int j = 0; j < C; ++j) t[j] = sq[j];
-  uint32_t pend = 0;
-#pragma unroll 1
-  for (int ii = 0; ii < L; ++ii) {
-    const uint32_t hv = SCR[ii * E];
-    uint32_t c1 = 0;
-#pragma unroll
-    for (int j = 0; j < C; ++j) {
-      const uint64_t p = mad(qh[j], hv, (uint64_t)t[j] + c1);
-      t[j] = (uint32_t)p;
-      c1 = (uint32_t)(p >> 32);
-    }
-    if (g == 0) BASE[ii * E] = t[0];
-    uint32_t in = from_next<G>(t[0]);
-    if (g == G - 1) in = 0;
-#pragma unroll
-    for (int j = 0; j < C - 1; ++j) t[j] = t[j + 1];
-    const uint64_t s = (uint64_t)in + pend + c1;
-    t[C - 1] = (uint32_t)s;
-    pend = (uint32_t)(s >> 32);
-  }
-  resolve_carries<C, G>(t, pend, g);
-  lds_sync();
-#pragma unroll
-  for (int j = 0; j < C; ++j) BASE[(L + g * C + j) * E] = t[j];
-  lds_sync();
+  scan_mul_add<C, G>(t, qh, SCR, BASE, E, g);
   if (wide) {
     uint32_t o[2 * C];
     from_lds<2 * C>(o, BASE, E, g);

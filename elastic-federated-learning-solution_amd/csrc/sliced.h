@@ -81,6 +81,11 @@ __device__ __forceinline__ void to_lds(uint32_t* base, int E, int g, const uint3
 #pragma unroll
   for (int j = 0; j < C; ++j) base[(g * C + j) * E] = x[j];
 }
+template <int C>
+__device__ __forceinline__ void from_lds(uint32_t (&x)[C], const uint32_t* base, int E, int g) {
+#pragma unroll
+  for (int j = 0; j < C; ++j) x[j] = base[(g * C + j) * E];
+}
 
 // lane's slice of a uniform number
 template <int C>
@@ -226,6 +231,41 @@ __device__ __forceinline__ void lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// t += q h by operand scanning over the L = C G words of h (word ii at h[ii * E] in LDS): word ii of
+// the sum leaves lane 0 into lo[ii * E] after step ii, and the high half follows at words
+// L .. 2 L - 1 of lo once its pending carries are resolved (it may lie over the words of h, all read
+// by then). Garner's join h q + s_q: on return the 2 L words are ready to read.
+template <int C, int G>
+__device__ __forceinline__ void scan_mul_add(uint32_t (&t)[C], const uint32_t (&q)[C], const uint32_t* h,
+                                             uint32_t* lo, int E, int g) {
+  constexpr int L = C * G;
+  uint32_t pend = 0;
+#pragma unroll 1
+  for (int ii = 0; ii < L; ++ii) {
+    const uint32_t hv = h[ii * E];
+    uint32_t c1 = 0;
+#pragma unroll
+    for (int j = 0; j < C; ++j) {
+      const uint64_t p = mad(q[j], hv, (uint64_t)t[j] + c1);
+      t[j] = (uint32_t)p;
+      c1 = (uint32_t)(p >> 32);
+    }
+    if (g == 0) lo[ii * E] = t[0];
+    uint32_t in = from_next<G>(t[0]);
+    if (g == G - 1) in = 0;
+#pragma unroll
+    for (int j = 0; j < C - 1; ++j) t[j] = t[j + 1];
+    const uint64_t s = (uint64_t)in + pend + c1;
+    t[C - 1] = (uint32_t)s;
+    pend = (uint32_t)(s >> 32);
+  }
+  resolve_carries<C, G>(t, pend, g);
+  lds_sync();
+#pragma unroll
+  for (int j = 0; j < C; ++j) lo[(L + g * C + j) * E] = t[j];
+  lds_sync();
 }
 
 // x -= m if cond; borrow rippled across the group (m: lane slice). cond uniform per group.

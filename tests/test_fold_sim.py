@@ -1,6 +1,6 @@
-"""The folded symmetric squaring's step algorithm (csrc/sliced28.h fold_*, build knob EFL_SQR_FOLD=1,
-off by default since it measured slower) simulated lane by lane on the CPU: squares and
-products equal the CIOS result (x + U m) / R bit for bit, accumulators within 64 bits."""
+"""The folded symmetric squaring's step algorithm (tools/fold_sim.py; its HIP code measured slower and
+was removed) simulated lane by lane on the CPU: squares and products equal the CIOS
+result (x + U m) / R bit for bit, accumulators within 64 bits."""
 import os
 import subprocess
 import sys

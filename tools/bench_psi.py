@@ -5,7 +5,7 @@ tests/golden/rsa_kat.json), kernel time between HIP events on the launch stream 
 launch. One JSON line per key into profiles/psi/bench_psi.jsonl (--out), each with
 
   * limb_products_issued: the v_mad_u64_u32 instructions one element's sign issues, counted from the
-    kernels' own loops (csrc/rsa.hip: the window walk over dp and dq as powm_window runs it; a CIOS
+    kernels' own loops (csrc/powm28.h: the window walk over dp and dq as powm_window runs it; a CIOS
     product 2 L28^2, a one-lane squaring C (C + 1) / 2 + C^2, an SOS squaring over two lanes
     C (C + 1) + 2 C ceil(C / 2) + 2 C L28; the 32-bit products of the reduction of x and of the
     join), and mad_peak_frac = issued per second over the measured v_mad_u64_u32 issue rate
@@ -34,7 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "elastic-federated-learning-solution_amd"))
 
 MAD_U64_U32_PEAK = 3.1722e13
-WINDOW = 5                     # csrc/rsa.hip kWin
+WINDOW = 5                     # csrc/powm28.h kWin
 CPU_PROCS = 16
 
 

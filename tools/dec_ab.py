@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
-"""Decryption A/B between library builds (run once per build, alternating, in one gpurun call; the
-build comes from EFL_HIP_LIB): CRT decryption of N int64 mantissas at the 2048- and 4096-bit keys
-(the G = 2 / G = 4 sliced families, round 6's folded squarings), timed with HIP events over `reps`
-launches, the plaintexts checked. One JSON line.
+"""Decryption A/B between library builds (run once per build, alternating, each run its own process;
+the build comes from EFL_HIP_LIB): CRT decryption of N int64 mantissas at the 1024-, 2048- and
+4096-bit keys (the default families: one lane, and the G = 2 / G = 4 sliced families with the SOS
+squarings), timed with HIP events over `reps` launches, the plaintexts checked. One JSON line.
 
-    EFL_HIP_LIB=.../libefl_hip_nofold.so python tools/dec_ab.py --label nofold
+Written for round 6's folded squarings; their HIP code has since been removed, the
+tool serves any two builds of the library.
+
+    EFL_HIP_LIB=.../libefl_hip_parent.so python tools/dec_ab.py --label parent
 """
 import argparse
 import json
@@ -30,7 +33,7 @@ def main():
     sh = st.cuda_stream
     pc.table_budget(16 << 30)
     out = {"tool": "dec_ab", "label": a.label, "library": efl.lib.version(), "keys": {}}
-    for n_bytes, N in ((256, 65536), (512, 65536)):
+    for n_bytes, N in ((128, 262144), (256, 65536), (512, 65536)):
         n, hs, p, q = pc.generate_keypair_ints(n_bytes, 24, random.Random(n_bytes))
         kp = efl.paillier.Keypair(seed=7)
         kp.set_keys_ints(n, hs, n_bytes // 2, 1, p, q, n_bytes)

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""CPU simulation of round 6's folded symmetric Montgomery squaring (csrc/sliced28.h fold_step,
-fold_pass, lazy_normalize_folded, normalize_folded; build knob EFL_SQR_FOLD=1), lane by lane, with
-Python integers standing in for the 64-bit accumulators. Each accumulator is checked against 2^64.
+"""CPU simulation of round 6's folded symmetric Montgomery squaring, lane by lane, with Python
+integers standing in for the 64-bit accumulators. Each accumulator is checked against 2^64. The HIP
+code it mirrored (csrc/sliced28.h fold_step, fold_pass, lazy_normalize_folded, normalize_folded behind
+the build knob EFL_SQR_FOLD) measured 3.9-4.6x slower and has been removed (DESIGN.md §6a names the
+last commit that held it); this simulation stays as the executable record of the algorithm.
 
 A square forms 2 a_i a_j once (at step min(i, j)) and a_i^2 once, and a product forms every a_j b_i.
 Either way the result must be (x + U m) / R, where U = -x m^-1 mod R and x = a^2 or a b. That is
