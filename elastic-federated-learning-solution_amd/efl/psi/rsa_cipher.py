@@ -3,7 +3,8 @@
 This is the level a caller with millions of IDs uses: numbers are rows of a device tensor, `int32`
 [n, words] (little-endian 32-bit words) or `uint8` [n, bytes] (the reference's wire form,
 int(v).to_bytes(byte_len, 'little'); [n, 4 * words] bytes are the same memory as [n, words] words,
-shorter rows are zero-extended). Every method returns rows of the form it was given. The signers of
+shorter rows are zero-extended, down to (n.bit_length() + 7) // 8 bytes: narrower rows could not hold
+every result and are refused). Every method returns rows of the form it was given. The signers of
 efl.psi.rsa_signer are thin list-of-int wrappers over it.
 """
 from __future__ import annotations
@@ -134,8 +135,14 @@ class RsaKey:
 
     # ---- rows ------------------------------------------------------------------------------
     def _rows(self, t, what):
-        """Device int32 [n, words] view (or zero-extended copy) of `t`, and how to give a result back."""
-        W = self.words
+        """Device int32 [n, words] view (or zero-extended copy) of `t`, and how to give a result back.
+
+        uint8 rows come back at the width they were given, so they must hold any result, a value
+        below n: at least (n.bit_length() + 7) // 8 bytes. Narrower rows are refused (by shape, before
+        anything runs): n.bit_length() // 8 bytes, the reference's wire length, hold every value only
+        when n's length is a multiple of 8 bits; for other keys pass wider rows, or int32 rows."""
+        info = self.info()
+        W = info.words
         if W == 0:
             raise errors.AbortedError("No public key.")
         t = _efl_lib.as_tensor(t)
@@ -151,6 +158,10 @@ class RsaKey:
         B = d.shape[1]
         if B > 4 * W:
             raise errors.InvalidArgumentError(f"{what}: rows of {B} bytes are longer than the key's {4 * W}")
+        if B < (info.n_bits + 7) // 8:
+            raise errors.InvalidArgumentError(
+                f"{what}: uint8 rows of {B} bytes cannot hold every value below an n of {info.n_bits} bits; "
+                f"pass rows of at least {(info.n_bits + 7) // 8} bytes")
         if B < 4 * W:
             d = torch.nn.functional.pad(d, (0, 4 * W - B))
         if d.data_ptr() % 16:

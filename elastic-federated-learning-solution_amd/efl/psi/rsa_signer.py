@@ -18,6 +18,9 @@ Deviations from the reference, all at its edges:
   - sign_blinded_ids_from_client takes items shorter than the key's row (zero-extended) and values
     >= n (reduced, as powmod does), and refuses items longer than the row with InvalidArgumentError,
     where the reference would sign any length.
+  - A value that n.bit_length() // 8 bytes do not hold (possible when n's length is no multiple of 8
+    bits) raises the reference's OverflowError wherever it would cross the wire, on the client
+    (_blind_ids) as on the server (sign_blinded_ids_from_client); nothing is ever cut short.
   - _deblind_signed_ids raises InvalidArgumentError naming the first blind number without an inverse
     (the reference's divm raises ZeroDivisionError).
   - _blind_ids draws its 256-bit blind numbers from os.urandom (the reference: random.SystemRandom,
@@ -44,6 +47,15 @@ def bytes2int(byte, byteorder='little'):
 
 def int2bytes(digit, byte_len, byteorder='little'):
     return int(digit).to_bytes(byte_len, byteorder)
+
+
+def wire_bytes(row, byte_len):
+    """int2bytes(v, byte_len) of a row's little-endian bytes: the first byte_len of them, or the
+    reference's OverflowError when a byte at or past byte_len is not zero. byte_len is
+    n.bit_length() // 8, which holds every value below n only when n's length is a multiple of 8 bits."""
+    if any(row[byte_len:]):
+        raise OverflowError("int too big to convert")
+    return bytes(row[:byte_len])
 
 
 def _cityhash64(text: str) -> int:
@@ -173,13 +185,7 @@ class ServerRsaSigner(RsaSigner):
         out = key.sign(rows.to(_device())).cpu().contiguous().numpy().tobytes()
         # a signature is below n, but n.bit_length() // 8 bytes hold it only when n's length is a
         # multiple of 8 bits (the reference's int2bytes raises OverflowError otherwise)
-        res = []
-        for i in range(len(ids)):
-            row = out[i * 4 * W:(i + 1) * 4 * W]
-            if any(row[byte_len:]):
-                raise OverflowError("int too big to convert")
-            res.append(row[:byte_len])
-        return res
+        return [wire_bytes(out[i * 4 * W:(i + 1) * 4 * W], byte_len) for i in range(len(ids))]
 
     def get_public_key_bytes(self):
         return self.pub_key_bytes_
@@ -208,7 +214,8 @@ class ClientRsaSigner(RsaSigner):
         key = self.key_
         W, byte_len = key.words, key.byte_len
         raw = rows.cpu().contiguous().numpy().tobytes()
-        return [raw[i * 4 * W:i * 4 * W + byte_len] for i in range(rows.shape[0])]
+        # a blinded value is below n: the server's rule (a value cut short would lose its ID silently)
+        return [wire_bytes(raw[i * 4 * W:(i + 1) * 4 * W], byte_len) for i in range(rows.shape[0])]
 
     def _blind_ids(self, ids, blind_numbers=None):
         key = self.key_
