@@ -9,6 +9,8 @@ Public names mirror efls-train/python/efl (exporter registry, efl/__init__.py:47
   efl.HexTensor (the DT_STRING stand-in), efl.lib.ops (the `fed_ops` namespace)
   efl.psi.{RsaSigner, ServerRsaSigner, ClientRsaSigner, RsaKey, pkcs1} (RSA blind-signature PSI)
   efl.psi.EccSigner, efl.psi.ecc_cipher.{x25519, x25519_hash} (ECDH PSI: batched X25519)
+  efl.psi.IdStore (the signed-ID store: a device hash table with the dict's semantics),
+  efl.psi.{EcdhJoinServer, EcdhJoinClient} (the ECDH join on top of it, without the transport)
 The kernels live in libefl_hip.so (C ABI: include/efl_hip.h); there is no CPU fallback.
 """
 from efl import exporter

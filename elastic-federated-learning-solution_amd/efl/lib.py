@@ -60,6 +60,13 @@ _SIGS = {
     # ECDH PSI (efl.psi.EccSigner): the scalar and the prefix are host bytes
     "efl_x25519": ([ctypes.c_char_p, _vp, _vp, _i64, _vp], _i32),
     "efl_x25519_hash": ([ctypes.c_char_p, ctypes.c_char_p, _i32, _vp, _vp, _vp, _i64, _vp], _i32),
+    # the signed-ID store (efl.psi.IdStore): caller-owned device buffers; efl_idset_hash takes host bytes
+    "efl_idset_hash": ([ctypes.c_uint64, ctypes.c_char_p, _i32], ctypes.c_uint64),
+    "efl_idset_scratch_bytes": ([_i64], _i64),
+    "efl_idset_insert": ([_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, ctypes.c_uint64, _vp, _vp, _i64, _vp],
+                         _i32),
+    "efl_idset_find": ([_vp, _i64, _i32, _vp, _vp, _i64, ctypes.c_uint64, _vp, _vp], _i32),
+    "efl_idset_rehash": ([_vp, _i32, _vp, _i64, _vp, _i64, ctypes.c_uint64, _vp], _i32),
 }
 for _name, (_args, _ret) in _SIGS.items():
     _f = getattr(_lib, _name)

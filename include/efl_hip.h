@@ -543,6 +543,47 @@ int efl_x25519(const uint8_t scalar[32], const uint8_t* u, uint8_t* out, int64_t
 int efl_x25519_hash(const uint8_t scalar[32], const char* prefix, int prefix_len, const char* chars,
                     const int64_t* offsets, uint8_t* out, int64_t n, void* stream);
 
+/* ---- Signed-ID store (efl.psi.IdStore) --------------------------------------------------------
+ * Replaces the Python dict the reference keeps its signed IDs in (efls-data/xfl/data/store/
+ * sample_kv_store.py, DictSampleKvStore) and the membership test of the join
+ * (xfl/service/data_join_server.py:95,216): a hash table over rows of `width` = 8 or 32 bytes
+ * (csrc/idset.h, csrc/idset.hip). Every buffer is the caller's, in device memory:
+ *   keys  [key_capacity][width]  the distinct rows in insertion order (8-byte aligned for width 8,
+ *                                16-byte aligned for width 32, as `rows` is)
+ *   slots [capacity] uint32      open addressing with linear probing, capacity a power of two up
+ *                                to 2^32; 0xFFFFFFFF = empty, otherwise an index into keys. A new
+ *                                store's slots are all 0xFFFFFFFF (efl_idset_rehash sets them).
+ *   size  one int64              the number of keys, read and advanced by the kernels
+ * The semantics are the dict's: a key's position is fixed by its first insertion; within a batch the
+ * lowest row index among equal rows is the one appended, new keys are appended in row order, and a
+ * row that is already a key is never appended. The load factor stays at or below 1/2: the caller
+ * passes size_bound >= *size (a host-side upper bound, so that no call reads *size back) and the
+ * entry points refuse capacity < 2 * (size_bound + n). A store holds at most 2^31 - 2 keys and a
+ * batch at most as many rows: RESOURCE_EXHAUSTED beyond that. n == 0 is a no-op, before anything
+ * else is looked at; a negative count, a null buffer, a misaligned row pointer, a width other than
+ * 8 or 32, a capacity that is not a power of two or is too small are INVALID_ARGUMENT before any HIP
+ * call. Stream-ordered, no host synchronisation, no allocation; no kernel waits for another lane. */
+/* The hash of a row under a store's seed, on the HOST (`row` is host memory of any alignment): the
+ * row's home slot is hash & (capacity - 1). 0 for a null row or a width other than 8 or 32. */
+uint64_t efl_idset_hash(uint64_t seed, const uint8_t* row, int width);
+/* Bytes of efl_idset_insert's scratch for a batch of n rows (0 for n <= 0 or n > 2^31 - 2). */
+int64_t efl_idset_scratch_bytes(int64_t n);
+/* Inserts the rows that are not keys yet; pos_out[i] (int64 [n]) <- the position of row i's key, new
+ * or old. key_capacity >= size_bound + n. `scratch` is device memory of scratch_len >=
+ * efl_idset_scratch_bytes(n) bytes, 4-byte aligned, free again once the call's work on `stream` is
+ * done. Five launches. `rows` must not overlap keys[size_bound ..]. */
+int efl_idset_insert(const uint8_t* rows, int64_t n, int width, uint8_t* keys, int64_t key_capacity,
+                     int64_t* size, int64_t size_bound, uint32_t* slots, int64_t capacity, uint64_t seed,
+                     int64_t* pos_out, void* scratch, int64_t scratch_len, void* stream);
+/* pos_out[i] <- the position of row i among the keys, or -1. */
+int efl_idset_find(const uint8_t* rows, int64_t n, int width, const uint8_t* keys, const uint32_t* slots,
+                   int64_t capacity, uint64_t seed, int64_t* pos_out, void* stream);
+/* Rebuilds `slots` (another capacity, another seed) from the first *size keys: every slot is set to
+ * empty, then each key claims the first empty slot of its chain. capacity >= 2 * size_bound;
+ * size_bound = 0 only clears the slots. */
+int efl_idset_rehash(const uint8_t* keys, int width, const int64_t* size, int64_t size_bound, uint32_t* slots,
+                     int64_t capacity, uint64_t seed, void* stream);
+
 /* ---- Key generation, HOST memory (GeneratePaillierKeypairOp, paillier.cc:833-904) ------------
  * The reference's keygen is a CPU op over GMP (mpz_probab_prime_p in find_prime, :851-863;
  * mpz_powm for hs, :884-888). These two are its arithmetic, on host buffers of little-endian
