@@ -176,8 +176,6 @@ struct Block {
   int64_t priv_off = 0, priv_words = 0;   // the private constants' reserved span of the head
   Big n, hs, n2, p, q, walk_start;
   bool has_walk = false, priv = false, has_table = false;
-  std::vector<uint32_t> head0;      // head and descriptor before the table was attached (drop_table)
-  efl_pl_key d0{};
   int a_bits = 0, g = 1, ln = 0, lc = 0, lh = 0;
   int W = 0, rows = 0, cols = 0, L28 = 0;   // the table's plan (L28 = 0: no radix-2^28 copy)
 
@@ -257,7 +255,15 @@ int write_private(Block& b, const Big& p, const Big& q) {
       set_error("private key does not fit the public key");
       return EFL_E_INVALID_ARGUMENT;
     }
-    hb::divmod(hb::sub(u, one), x, &l, nullptr);
+    // L is defined on u = 1 mod x only (mpz_l_func divides exactly, paillier.cc:23-26), and
+    // (x - 1) n mod x^2 is a multiple of x exactly when x divides n: a prime of another key would
+    // give hp, hq with which no decryption can be right, so it is refused like p == q
+    Big rem;
+    hb::divmod(hb::sub(u, one), x, &l, &rem);
+    if (!rem.zero()) {
+      set_error("private key does not fit the public key: %c does not divide n", s ? 'q' : 'p');
+      return EFL_E_INVALID_ARGUMENT;
+    }
     Big inv;
     if (!hb::modinv(l, x, &inv)) {
       // mpz_invert fails and the reference keeps a stale hp; no decryption can be right then
@@ -601,7 +607,9 @@ int attach(Block& b, hipStream_t s) {
 }
 
 // head + table in one allocation, the table built now. The table's bytes are reserved in the
-// process budget first (atomically); on any failure the block is left with no device allocation.
+// process budget first (atomically). When that reservation is refused nothing has been touched: the
+// block keeps the allocation it had. On a failure after it (upload, build, attach) the block is
+// left with no device allocation (b.dev null) and the bytes are back in the budget.
 int realise_with_table(Block& b, hipStream_t s) {
   const int64_t tb = planned_table_bytes(b);
   if (!budget_try_take(tb)) {
@@ -609,8 +617,6 @@ int realise_with_table(Block& b, hipStream_t s) {
               "table budget; efl_pl_table_budget)", (long long)tb);
     return EFL_E_RESOURCE_EXHAUSTED;
   }
-  b.head0 = b.head;
-  b.d0 = b.d;
   const int rc0 = upload(b, true, s);
   if (rc0 != EFL_OK) {
     budget_give(tb);
@@ -625,12 +631,19 @@ int realise_with_table(Block& b, hipStream_t s) {
 
 // back to the table-less head in a fresh allocation (the table's bytes go back to the budget):
 // after a failed table build (whose upload had already let the old allocation go), or to hand a
-// key owner's unused n^2 table to its CRT sub-tables. The previous error text is kept.
+// key owner's unused n^2 table to its CRT sub-tables. The table-less head is the CURRENT head and
+// descriptor with the table fields cleared (attach sets nothing else), so a private key written in
+// place after the table was built (efl_pl_set_private) stays. Not for a block with a walk start,
+// whose head attach changes (only the CRT sub-keys have one, and they are never dropped this way).
+// The previous error text is kept.
 int drop_table(Block& b, hipStream_t s) {
-  if (!b.head0.empty()) {
-    b.head = b.head0;
-    b.d = b.d0;
+  if (b.has_walk) {
+    set_error("internal: drop_table on a key block with a walk start");
+    return EFL_E_INTERNAL;
   }
+  b.d.off_table = -1;
+  b.d.off_table28 = -1;
+  b.d.table_rows = 0;
   const std::string err = efl_last_error();
   const int rc = upload(b, false, s);
   if (rc == EFL_OK) set_error("%s", err.c_str());
@@ -812,11 +825,12 @@ int ensure_table(efl_pl_ctx* c, hipStream_t s) {
   const int rc = realise_with_table(b, s);
   ++c->generation;
   if (rc != EFL_OK) {
-    // the failed build had let the old allocation go: put the table-less head back, so every entry
-    // point still finds a live key block; if not even that works, the context holds no
-    // key ("No public key.") rather than a dangling block. The build's error is what is reported.
+    // a build that failed after its upload had let the old allocation go: put the table-less head
+    // back, so every entry point still finds a live key block; if not even that works,
+    // the context holds no key ("No public key.") rather than a dangling block. A refused budget
+    // reservation left the block as it was. The build's error is what is reported.
     const std::string err = efl_last_error();
-    if (drop_table(b, s) != EFL_OK) {
+    if (!b.dev && drop_table(b, s) != EFL_OK) {
       c->drop_crt();
       c->main.reset();
     }

@@ -409,7 +409,9 @@ int efl_pl_set_public(efl_pl_ctx* ctx, const char* n_hex, int n_bytes, const cha
 int efl_pl_set_keypair(efl_pl_ctx* ctx, const char* n_hex, int n_bytes, const char* hs_hex, int a_bytes,
                        int group_size, const char* p_hex, const char* q_hex, void* stream);
 /* SetPaillierPrivateKey(p, q): ignored without a public key (paillier.cc:88-91). p, q distinct odd
- * (INVALID_ARGUMENT otherwise, where the reference's mpz_invert would fail silently). */
+ * divisors of n (INVALID_ARGUMENT otherwise, where the reference's mpz_invert would fail silently
+ * or its mpz_divexact is undefined; the key set before stays as it was). In place when the primes
+ * fit the key block's limb class: the public part and a table already built do not change. */
 int efl_pl_set_private(efl_pl_ctx* ctx, const char* p_hex, const char* q_hex, void* stream);
 /* The key block and descriptor every efl_pl_* op above takes: which 0 = the key, 1 / 2 = the key
  * owner's CRT sub-keys (p, hs mod p^2) / (q, hs mod q^2) (after EFL_PL_PREPARE_CRT). ABORTED "No

@@ -3,7 +3,8 @@ buffers, and neither the efl Python package nor the oracle. This is what a Tenso
 binding CreatePaillierKeypair / SetPaillierPublicKey / SetPaillierPrivateKey
 (paillier.cc:337-441) does: hex text in, an opaque context out, the key block and its
 descriptor fetched from the library. The known answers are GMP 6.2.1's (tests/golden/paillier_kat.json).
-Also the process-wide table budget (gmp_utils.h:20 / paillier.cc:399-401's ResourceExhausted)."""
+Also the process-wide table budget (gmp_utils.h:20 / paillier.cc:399-401's ResourceExhausted). The
+last test alone goes through the package: the same order of calls as its Python handle makes them."""
 import ctypes
 import json
 import os
@@ -313,10 +314,60 @@ def test_public_then_private_gives_crt_the_whole_budget(lib):
                 assert inf["crt"] == 1 and inf["has_table"] == (0 if released else 1), (budget, inf)
                 if released:
                     assert inf["table_bytes"] == 0 and inf["crt_table_window"] == want, (inf, want)
+                # the private key written in place survives the release: decryption through the
+                # context and through the stateless entry point on the block fetched after it
+                mag = torch.empty((N, ln), dtype=torch.int32, device="cuda")
+                neg = torch.empty(N, dtype=torch.int8, device="cuda")
+                ok(lib, lib.efl_pl_ctx_decrypt(b.h, c1.data_ptr(), mag.data_ptr(), neg.data_ptr(), N, stream()))
+                assert [(-x if s else x) for x, s in zip(ints(mag), neg.cpu().tolist())] == m.cpu().tolist()
+                blk, desc = vp(), ctypes.create_string_buffer(DESC_BYTES)
+                ok(lib, lib.efl_pl_ctx_key(b.h, 0, ctypes.byref(blk), desc))
+                mag2 = torch.zeros_like(mag)
+                ok(lib, lib.efl_pl_decrypt(blk, desc, c1.data_ptr(), mag2.data_ptr(), neg.data_ptr(), N, stream()))
+                assert torch.equal(mag2, mag)
                 ok(lib, lib.efl_pl_ctx_encrypt(b.h, m.data_ptr(), None, c2.data_ptr(), N, 9, 3, 1, stream()))
                 assert torch.equal(c1, c2)
+                ok(lib, lib.efl_pl_ctx_decrypt(b.h, c2.data_ptr(), mag2.data_ptr(), neg.data_ptr(), N, stream()))
+                assert torch.equal(mag2, mag)
             finally:
                 a.close()
                 b.close()
     finally:
         lib.efl_pl_table_budget(prev, None)
+
+
+def test_public_then_private_through_the_package():
+    """The reference's own call order end to end through the package: KeyBlock(n, hs) (the public key;
+    its n^2 table is built), .set_private(p, q) in place, then one efl.paillier encryption, whose CRT
+    route releases the table under a budget that binds (tests/keyctx_model.py chooses it), and the
+    decryption of its ciphertexts."""
+    import efl
+    import keyctx_model as km
+    from efl.privacy import paillier_cipher as pc
+    k = KEYS[0]
+    n, hs, p, q = (int(k[f], 16) for f in ("n", "hs", "p", "q"))
+    _, budgets, _, _ = km.plan()
+    prev, used = pc.table_budget()
+    kp = efl.paillier.Keypair(seed=11)
+    try:
+        pc.table_budget(used + budgets["binding"])
+        kp._key = key = pc.KeyBlock(n, hs, k["a_bits"], 1, max_bytes=km.CONTEXT_CAP, n_bytes=k["n_bytes"])
+        assert key.has_table and not key.info().has_private
+        key.set_private(p, q)
+        assert key.has_table and key.info().has_private and key.crt_capable()
+        m = torch.tensor([0, -1, 2**63 - 1, -2**63, 12345, -98765], dtype=torch.int64)
+        ct = kp.encrypt(m, counter_base=7)
+        i = key.info()
+        assert (i.crt, i.has_table, i.has_private, i.table_bytes) == (1, 0, 1, 0)
+        assert key.desc.has_private == 1 and key.desc.off_table == -1
+        assert kp.decrypt(ct, dtype=torch.int64).cpu().tolist() == m.tolist()
+        pub = efl.paillier.Keypair(seed=11)
+        pub._key = pc.KeyBlock(n, hs, k["a_bits"], 1, max_bytes=km.CONTEXT_CAP, n_bytes=k["n_bytes"])
+        try:
+            assert pub.encrypt(m, counter_base=7).tensor.to_hex().strings() == ct.tensor.to_hex().strings()
+        finally:
+            pub._key.close()
+    finally:
+        if kp._key is not None:
+            kp._key.close()
+        pc.table_budget(prev)
