@@ -11,6 +11,7 @@ Public names mirror efls-train/python/efl (exporter registry, efl/__init__.py:47
   efl.psi.EccSigner, efl.psi.ecc_cipher.{x25519, x25519_hash} (ECDH PSI: batched X25519)
   efl.psi.IdStore (the signed-ID store: a device hash table with the dict's semantics),
   efl.psi.{EcdhJoinServer, EcdhJoinClient} (the ECDH join on top of it, without the transport)
+  efl.psi.{RsaJoinServer, RsaJoinClient} (the RSA join), efl.psi.rsa_cipher.{decimal_rows, oneway_rows}
 The kernels live in libefl_hip.so (C ABI: include/efl_hip.h); there is no CPU fallback.
 """
 from efl import exporter

@@ -57,6 +57,10 @@ _SIGS = {
     "efl_rsa_blind": ([_vp, _vp, _vp, _vp, _i64, _vp], _i32),
     "efl_rsa_unblind": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp], _i32),
     "efl_sha256_fdh": ([_vp, _vp, _vp, _i32, _i64, _vp], _i32),
+    # the tail of a signature: the decimal text of rows and a 64-bit one-way hash over it
+    "efl_rsa_decimal_digits": ([_i32], _i32),
+    "efl_rsa_decimal": ([_vp, _i32, _i64, _vp, _i64, _vp, _vp], _i32),
+    "efl_rsa_oneway": ([_vp, _i32, _i64, _i32, _vp, _vp], _i32),
     # ECDH PSI (efl.psi.EccSigner): the scalar and the prefix are host bytes
     "efl_x25519": ([ctypes.c_char_p, _vp, _vp, _i64, _vp], _i32),
     "efl_x25519_hash": ([ctypes.c_char_p, ctypes.c_char_p, _i32, _vp, _vp, _vp, _i64, _vp], _i32),

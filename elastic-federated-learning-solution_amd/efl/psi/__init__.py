@@ -1,10 +1,11 @@
 """efl.psi - sample alignment by private set intersection on the GPU, both protocols of the
 reference's efls-data/xfl/data/psi: RSA blind signatures (rsa_signer.py: the signers with the
-reference's names, the key context over device tensors (RsaKey) and the PKCS#1 key reader / writer)
-and ECDH over curve25519 (ecc_signer.py: EccSigner, and batched X25519 over uint8 rows in
-ecc_cipher); and what the signed IDs go into: IdStore (id_store.py), the reference's SampleKvStore
-as a hash table in device memory, and the transport-free ECDH join on top of it (ecdh_join.py:
-EcdhJoinServer, EcdhJoinClient)."""
+reference's names, the key context over device tensors (RsaKey), the decimal text and one-way hash of
+a signature (rsa_cipher) and the PKCS#1 key reader / writer) and ECDH over curve25519 (ecc_signer.py:
+EccSigner, and batched X25519 over uint8 rows in ecc_cipher); and what the signed IDs go into: IdStore
+(id_store.py), the reference's SampleKvStore as a hash table in device memory, and the transport-free
+joins on top of it (ecdh_join.py: EcdhJoinServer, EcdhJoinClient; rsa_join.py: RsaJoinServer,
+RsaJoinClient)."""
 from efl.psi import pkcs1
 from efl.psi import rsa_cipher
 from efl.psi import rsa_signer
@@ -12,11 +13,14 @@ from efl.psi import ecc_cipher
 from efl.psi import ecc_signer
 from efl.psi import id_store
 from efl.psi import ecdh_join
+from efl.psi import rsa_join
 from efl.psi.rsa_cipher import RsaKey
 from efl.psi.rsa_signer import RsaSigner, ServerRsaSigner, ClientRsaSigner
 from efl.psi.ecc_signer import EccSigner
 from efl.psi.id_store import IdStore
 from efl.psi.ecdh_join import EcdhJoinServer, EcdhJoinClient
+from efl.psi.rsa_join import RsaJoinServer, RsaJoinClient
 
 __all__ = ["RsaSigner", "ServerRsaSigner", "ClientRsaSigner", "RsaKey", "EccSigner", "IdStore", "EcdhJoinServer",
-           "EcdhJoinClient", "pkcs1", "rsa_cipher", "rsa_signer", "ecc_cipher", "ecc_signer", "id_store", "ecdh_join"]
+           "EcdhJoinClient", "RsaJoinServer", "RsaJoinClient", "pkcs1", "rsa_cipher", "rsa_signer", "ecc_cipher",
+           "ecc_signer", "id_store", "ecdh_join", "rsa_join"]

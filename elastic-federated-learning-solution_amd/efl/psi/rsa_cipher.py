@@ -6,10 +6,16 @@ int(v).to_bytes(byte_len, 'little'); [n, 4 * words] bytes are the same memory as
 shorter rows are zero-extended, down to (n.bit_length() + 7) // 8 bytes: narrower rows could not hold
 every result and are refused). Every method returns rows of the form it was given. The signers of
 efl.psi.rsa_signer are thin list-of-int wrappers over it.
+
+Beside the key: the tail of a signature, hex(OneWayHash(str(v)))[2:] in the reference. decimal_rows is
+Python's str(int) of every row on the device (efl_rsa_decimal), oneway_rows a 64-bit one-way hash over
+that text as uint8 [n, 8] rows (efl_rsa_oneway; ONEWAY_HASHES names the device's hashes, oneway_sha256
+is the host twin), oneway_text a row's reference byte string.
 """
 from __future__ import annotations
 
 import ctypes
+import hashlib
 
 import numpy as np
 import torch
@@ -74,6 +80,100 @@ def ints_from_rows(rows: torch.Tensor) -> list:
     raw = a.tobytes()
     k = a.shape[1] * a.itemsize if a.ndim == 2 and a.shape[0] else 0
     return [int.from_bytes(raw[i * k:(i + 1) * k], "little") for i in range(a.shape[0])]
+
+
+# ---- the tail of a signature: decimal text and one-way hash (efl_rsa_decimal, efl_rsa_oneway) ----
+
+MAX_DECIMAL_WORDS = 128
+# the device's one-way hashes by name: the `hash` argument of efl_rsa_oneway
+ONEWAY_HASHES = {"sha256": 1}
+
+
+def oneway_sha256(text: str) -> int:
+    """The host twin of ONEWAY_HASHES["sha256"] (EFL_ONEWAY_SHA256_64), a callable for the signers'
+    oneway_hash=: the first 8 bytes of sha256(text) as a big-endian number."""
+    return int.from_bytes(hashlib.sha256(text.encode("utf-8")).digest()[:8], "big")
+
+
+def oneway_text(row8) -> bytes:
+    """The reference's byte string hex(v)[2:] of one row of oneway_rows (8 bytes, v little-endian)."""
+    if isinstance(row8, torch.Tensor):
+        row8 = row8.detach().cpu().contiguous().numpy().tobytes()
+    row8 = bytes(row8)
+    if len(row8) != 8:
+        raise errors.InvalidArgumentError(f"oneway_text: a row is 8 bytes, got {len(row8)}")
+    return hex(int.from_bytes(row8, "little"))[2:].encode()
+
+
+def oneway_texts(rows8) -> list:
+    """oneway_text of every row of a uint8 [n, 8] tensor: one copy to the host."""
+    raw = rows8.detach().cpu().contiguous().numpy().tobytes()
+    return [hex(int.from_bytes(raw[o:o + 8], "little"))[2:].encode() for o in range(0, len(raw), 8)]
+
+
+def _number_rows(rows, what):
+    """Device int32 [n, words] rows of `int32` [n, words] or `uint8` [n, bytes] rows (the bytes
+    zero-extended to whole words), 1 <= words <= 128: the forms RsaKey._rows takes, without a key."""
+    t = _efl_lib.as_tensor(rows)
+    if t.dim() != 2:
+        raise errors.InvalidArgumentError(f"{what}: rows must be a 2-D tensor, got shape {tuple(t.shape)}")
+    if t.dtype not in (torch.int32, torch.uint8):
+        raise errors.InvalidArgumentError(f"{what}: rows must be int32 or uint8, got {t.dtype}")
+    words = t.shape[1] if t.dtype == torch.int32 else (t.shape[1] + 3) // 4
+    if not 1 <= words <= MAX_DECIMAL_WORDS:
+        raise errors.InvalidArgumentError(
+            f"{what}: rows of {t.shape[1]} {'words' if t.dtype == torch.int32 else 'bytes'}: a number has 1 to "
+            f"{MAX_DECIMAL_WORDS} words")
+    d, _ = _efl_lib.on_device(t)
+    if d.dtype == torch.uint8:
+        if d.shape[1] % 4:
+            d = torch.nn.functional.pad(d, (0, 4 * words - d.shape[1]))
+        if d.data_ptr() % 4:
+            d = d.clone()
+        d = d.view(torch.int32)
+    elif d.data_ptr() % 4:
+        d = d.clone()
+    return d, words
+
+
+def decimal_rows(rows, stride=None):
+    """Python's str(int) of every row on the device (efl_rsa_decimal): (text uint8 [n, stride], len
+    int32 [n]); row i's digits are text[i, stride - len[i]:], the bytes before them are b"0". stride
+    defaults to efl_rsa_decimal_digits(words), the most digits a row can have."""
+    d, words = _number_rows(rows, "decimal_rows")
+    digits = int(_lib.efl_rsa_decimal_digits(words))
+    stride = digits if stride is None else int(stride)
+    if stride < digits:
+        raise errors.InvalidArgumentError(f"decimal_rows: stride {stride} is below the {digits} digits of {words} words")
+    n = d.shape[0]
+    text = torch.empty((n, stride), dtype=torch.uint8, device=d.device)
+    ln = torch.empty(n, dtype=torch.int32, device=d.device)
+    if n:
+        _efl_lib.check(_lib.efl_rsa_decimal(d.data_ptr(), words, n, text.data_ptr(), stride, ln.data_ptr(),
+                                            _efl_lib.stream_handle(d.device)))
+    return text, ln
+
+
+def decimal_strings(rows) -> list:
+    """[str(v)] of the rows: decimal_rows, one copy to the host, then slices."""
+    text, ln = decimal_rows(rows)
+    stride = text.shape[1]
+    raw = text.cpu().numpy().tobytes()
+    return [raw[(i + 1) * stride - k:(i + 1) * stride].decode("ascii") for i, k in enumerate(ln.tolist())]
+
+
+def oneway_rows(rows, hash="sha256") -> torch.Tensor:
+    """uint8 [n, 8] on the device: ONEWAY_HASHES[hash] of str(v) of every row, the 64-bit value
+    little-endian (efl_rsa_oneway); rows for an IdStore(8), oneway_text gives a row's reference form."""
+    if hash not in ONEWAY_HASHES:
+        raise errors.InvalidArgumentError(f"oneway_rows: hash {hash!r} is not one of {sorted(ONEWAY_HASHES)}")
+    d, words = _number_rows(rows, "oneway_rows")
+    n = d.shape[0]
+    out = torch.empty((n, 8), dtype=torch.uint8, device=d.device)
+    if n:
+        _efl_lib.check(_lib.efl_rsa_oneway(d.data_ptr(), words, n, ONEWAY_HASHES[hash], out.data_ptr(),
+                                           _efl_lib.stream_handle(d.device)))
+    return out
 
 
 class RsaKey:

@@ -10,9 +10,16 @@ strings on the wire are the reference's, int(v).to_bytes(n.bit_length() // 8, 'l
 Deviations from the reference, all at its edges:
   - Keys are PKCS#1 PEM / DER read and written by efl.psi.pkcs1 (the `rsa` package is not needed);
     load_key returns its named tuples (fields n, e and, private, d, p, q).
-  - The final one-way hash is a constructor argument, `oneway_hash=`, a callable from str to int. The
-    default is cityhash.CityHash64, imported when oneway_hash_list first runs. That step stays on the
-    host: it hashes the DECIMAL text of each signature.
+  - The final one-way hash is a constructor argument, `oneway_hash=`: a callable from str to int, or
+    the name of a device hash (rsa_cipher.ONEWAY_HASHES: "sha256", whose host twin is
+    rsa_cipher.oneway_sha256). The default, None, is cityhash.CityHash64, imported when a hash first
+    runs. It hashes the DECIMAL text of each signature: with a name the text and the hash are made
+    on the GPU (efl_rsa_oneway); with a callable the batch methods below take the text from the GPU
+    (efl_rsa_decimal) and call the hash once per string.
+  - sign_rows, sign_blinded_rows, blind_rows and deblind_rows are the signers over device tensors:
+    a batch is never cut into Python ints, and a signed ID is a row of a uint8 [n, 8] tensor (the
+    64-bit hash little-endian; rsa_cipher.oneway_text gives the reference's byte string), what an
+    IdStore(8) and efl.psi.rsa_join take.
   - oneway_hash_list and rsa_sign_list are methods, not static: the first needs the hash, the second
     signs by CRT with the loaded private key (d and n, when given, must be that key's).
   - sign_blinded_ids_from_client takes items shorter than the key's row (zero-extended) and values
@@ -33,6 +40,7 @@ import math
 import os
 import secrets
 
+import numpy as np
 import torch
 
 from efl import errors
@@ -72,6 +80,9 @@ class RsaSigner(object):
     """RSA signer base."""
 
     def __init__(self, oneway_hash=None):
+        if isinstance(oneway_hash, str) and oneway_hash not in rsa_cipher.ONEWAY_HASHES:
+            raise errors.InvalidArgumentError(
+                f"oneway_hash {oneway_hash!r}: a callable, None, or one of {sorted(rsa_cipher.ONEWAY_HASHES)}")
         self.oneway_hash_ = oneway_hash
         self._key = None                  # RsaKey: the device context, made on first use
         self._key_numbers = None          # set by the subclasses: (n, e) or (n, e, d, p, q)
@@ -131,8 +142,44 @@ class RsaSigner(object):
         return vals if ret_int else [format(v, "064x") for v in vals]
 
     def oneway_hash_list(self, ids):
+        if isinstance(self.oneway_hash_, str):
+            return self._oneway_named_list(list(ids), self.oneway_hash_)
         h = self.oneway_hash_ or _cityhash64
         return [hex(h(str(item)))[2:].encode('utf-8') for item in ids]
+
+    @staticmethod
+    def _oneway_named_list(ids, name):
+        """oneway_hash_list with a device hash: the non-negative ints below 2^4096 in one batch on the
+        GPU, any other item through the host twin on str(item), as the reference would hash it."""
+        twin = _HOST_TWINS[name]
+        out = [None] * len(ids)
+        on_device = [i for i, v in enumerate(ids)
+                     if isinstance(v, int) and not isinstance(v, bool) and 0 <= v < _DEVICE_BOUND]
+        if on_device:
+            vals = [ids[i] for i in on_device]
+            words = max(1, (max(v.bit_length() for v in vals) + 31) // 32)
+            rows = rsa_cipher.oneway_rows(rsa_cipher.rows_from_ints(vals, words).to(_device()), name)
+            for i, text in zip(on_device, rsa_cipher.oneway_texts(rows)):
+                out[i] = text
+        for i, v in enumerate(ids):
+            if out[i] is None:
+                out[i] = hex(twin(str(v)))[2:].encode('utf-8')
+        return out
+
+    def _oneway_rows(self, rows):
+        """The one-way hash of every row of signatures as uint8 [n, 8] on the device: the device hash,
+        or the decimal strings from the device through the callable (its result's 8 bytes, little-endian)."""
+        if isinstance(self.oneway_hash_, str):
+            return rsa_cipher.oneway_rows(rows, self.oneway_hash_)
+        h = self.oneway_hash_ or _cityhash64
+        vals = [int(h(s)) for s in rsa_cipher.decimal_strings(rows)]
+        for i, v in enumerate(vals):
+            if not 0 <= v < 2 ** 64:
+                raise errors.InvalidArgumentError(f"the one-way hash of signature {i} does not fit 64 bits")
+        buf = bytearray(b"".join(v.to_bytes(8, "little") for v in vals))
+        host = torch.frombuffer(buf, dtype=torch.uint8).view(len(vals), 8) if vals else \
+            torch.empty((0, 8), dtype=torch.uint8)
+        return host.to(_device())
 
     def rsa_sign_list(self, ids, d=None, n=None):
         """[x^d mod n] as ints, by CRT on the GPU with the loaded private key."""
@@ -150,6 +197,10 @@ class RsaSigner(object):
 def _device():
     from efl import lib
     return lib.require_gpu()
+
+
+_HOST_TWINS = {"sha256": rsa_cipher.oneway_sha256}
+_DEVICE_BOUND = 1 << (32 * rsa_cipher.MAX_DECIMAL_WORDS)
 
 
 class ServerRsaSigner(RsaSigner):
@@ -186,6 +237,20 @@ class ServerRsaSigner(RsaSigner):
         # a signature is below n, but n.bit_length() // 8 bytes hold it only when n's length is a
         # multiple of 8 bits (the reference's int2bytes raises OverflowError otherwise)
         return [wire_bytes(out[i * 4 * W:(i + 1) * 4 * W], byte_len) for i in range(len(ids))]
+
+    def sign_rows(self, ids):
+        """sign_func over tensors: uint8 [n, 8] on the device, row i the one-way hash of the signature of
+        ids[i] (oneway_text of it is sign_func's item i)."""
+        key = self.key_
+        return self._oneway_rows(key.sign(RsaSigner._fdh_rows(list(ids), key.words)))
+
+    def sign_blinded_rows(self, rows):
+        """PsiSign over tensors: the signatures of `int32` [n, words] rows of blinded hashes, where the
+        rows were."""
+        t = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(rows)
+        if t.dtype != torch.int32:
+            raise errors.InvalidArgumentError(f"sign_blinded_rows: rows must be int32 [n, words], got {t.dtype}")
+        return self.key_.sign(t)
 
     def get_public_key_bytes(self):
         return self.pub_key_bytes_
@@ -229,6 +294,32 @@ class ClientRsaSigner(RsaSigner):
         h = rsa_cipher.rows_from_ints(ids, key.words).to(dev)
         r = rsa_cipher.rows_from_ints(blind_numbers, key.words).to(dev)
         return self._wire(key.blind(h, r)), blind_numbers
+
+    def blind_rows(self, ids, blind_numbers=None):
+        """_blind_ids over tensors: (blinded, r), both `int32` [n, words] on the device; blinded goes to
+        the server's sign_blinded_rows, r stays here for deblind_rows. The 256-bit blind numbers are
+        one os.urandom(32 n), a zero redrawn; blind_numbers= fixes them for tests."""
+        key = self.key_
+        ids = list(ids)
+        n, W = len(ids), key.words
+        if blind_numbers is None:
+            a = np.frombuffer(os.urandom(32 * n), dtype="<i4").reshape(n, 8).copy()
+            for i in np.flatnonzero(~a.any(axis=1)):
+                a[i] = np.frombuffer(int2bytes(self._draw_blind_number(), 32), dtype="<i4")
+            r = torch.zeros((n, W), dtype=torch.int32)
+            r[:, :8] = torch.from_numpy(a)
+        else:
+            blind_numbers = [int(x) for x in blind_numbers]
+            if len(blind_numbers) != n:
+                raise errors.InvalidArgumentError("as many blind numbers as ids")
+            r = rsa_cipher.rows_from_ints(blind_numbers, W)
+        r = r.to(_device())
+        return key.blind(RsaSigner._fdh_rows(ids, W), r), r
+
+    def deblind_rows(self, signed, r):
+        """_deblind_signed_ids over tensors: uint8 [n, 8] on the device, the one-way hash of signed
+        r^-1 mod n. InvalidArgumentError naming the first blind number without an inverse."""
+        return self._oneway_rows(self.key_.unblind(signed, r))
 
     def _deblind_signed_ids(self, signed_blinded_hashed_ids, blind_numbers):
         key = self.key_

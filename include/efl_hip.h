@@ -526,6 +526,31 @@ int efl_rsa_unblind(efl_rsa_ctx* ctx, const uint32_t* s, const uint32_t* r, uint
 int efl_sha256_fdh(const char* chars, const int64_t* offsets, uint32_t* out, int words_per_row, int64_t n,
                    void* stream);
 
+/* The tail of a signature, hex(OneWayHash(str(v)))[2:] (rsa_signer.py:66-67,90,122), on the device
+ * (csrc/decimal.h, csrc/decimal.hip). Rows here are any `words` little-endian 32-bit words,
+ * 1 <= words <= 128, 4-byte aligned; no key context. n == 0 is a no-op; a negative count, words out
+ * of range, a null or misaligned buffer, a stride below efl_rsa_decimal_digits(words) or above 2^30
+ * and an unknown hash are INVALID_ARGUMENT before any HIP call. Both take stream-ordered scratch
+ * (hipMallocAsync / hipFreeAsync on `stream`): ceil(digits / 9) + 1 words for each of up to 2^18 rows
+ * per launch, the rows' 9-digit chunks. No host synchronisation. */
+/* Most digits a row of `words` words can have; 0 unless 1 <= words <= 128. Host only. */
+int efl_rsa_decimal_digits(int words);
+/* Python's str(int) of every row: text[i*stride .. (i+1)*stride) holds the digits RIGHT-aligned and
+ * left-padded with ASCII '0', len[i] = the digits without padding (1 for a zero row).
+ * stride >= efl_rsa_decimal_digits(words). Every byte of text is written. n == 0 writes nothing.
+ * Two launches per 2^18 rows: the chunks, then the text in aligned dword stores (text may have any
+ * alignment: the bytes before the first and after the last aligned dword are stored singly). */
+int efl_rsa_decimal(const uint32_t* x, int words, int64_t n, uint8_t* text, int64_t stride,
+                    int32_t* len, void* stream);
+/* out[i] = H(the len[i] digits of row i) as 8 bytes, the 64-bit value little-endian; out is 8-byte
+ * aligned, [n][8]: rows of an 8-byte-wide signed-ID store.
+ * hash: EFL_ONEWAY_SHA256_64 = 1, the first 8 bytes of the SHA-256 digest read as a big-endian
+ * number. Any other value: INVALID_ARGUMENT.
+ * Not fused with the conversion: the chunks go through the scratch above and the hash kernel reads
+ * its digits from them, so the text itself is never written, neither to LDS nor to memory. */
+#define EFL_ONEWAY_SHA256_64 1
+int efl_rsa_oneway(const uint32_t* x, int words, int64_t n, int hash, uint8_t* out, void* stream);
+
 /* ---- ECDH PSI (efl.psi.EccSigner) ------------------------------------------------------------
  * Replaces the per-ID curve25519-donna calls of efls-data/xfl/data/psi/ecc_signer.py (sign_hash for
  * every local ID, sign for every item of the peer): X25519 of RFC 7748 with one scalar for the whole
