@@ -319,9 +319,14 @@ int efl_pl_invert(const void* key_block, const efl_pl_key* key, const uint32_t* 
  * (x^|y|)^(2^(xe + ye - min)) are multiplied into z_pos (y > 0) or z_neg (y < 0); the caller
  * finishes z = z_pos * z_neg^-1 (efl_pl_invert + efl_pl_add). With the radix-2^28 family the
  * kernels first write x R mod n^2 and its odd powers for every x (u*v*16 padded radix-2^28
- * numbers), then every output's multiply schedule (u*w*S lists of up to 5*ceil(v/S) 32-bit words,
- * S the term split) into scratch taken and released on `stream` (hipMallocAsync / hipFreeAsync);
- * a failed allocation returns the HIP error. An output squares its accumulator once per bit level,
+ * numbers), then every output's multiply schedule (u*w*S lists of 32-bit words, S the term split)
+ * into scratch taken and released on `stream` (hipMallocAsync / hipFreeAsync); a failed allocation
+ * returns the HIP error. A list holds up to cap words, one per 5-bit window of a term's |y|:
+ * cap = min(5*ceil(v/S), 4096), lowered to 2^28 / (u*w*S) where all the lists together would pass
+ * 2^28 words (1 GiB). A split's schedule is not listed, and its group scans its terms at every bit
+ * level instead (the same result, slower), when it has more than cap windows, a top bit level past
+ * 1024 (the word's 10-bit level field), or more than 65,536 terms (its 16-bit term field; S, or
+ * efl_pl_tune(ln, 3, S), divides wider products). An output squares its accumulator once per bit level,
  * up to the exponent spread (max - min of xe + ye over its terms) plus the top bit of |y|: the
  * Python host runs a product whose spread may pass 65536 term by term instead (PaillierMulScalar,
  * chunked PaillierMulExp2, PaillierAdd), so no launch loops that long. */
