@@ -15,6 +15,10 @@
 // mul and sqr take loose operands: a column is at most 77 E^2 + 190 O^2 < 2^62.2 for even limbs
 // below E = 3 2^26 and odd limbs below O = 3 2^25 + 2^16, and the premultiplied operands 19 E and
 // 4 O stay below 2^32.
+//
+// FE_AUDIT(site, fe, cls) stands where a function states the class of an operand or of its result.
+// It expands to nothing unless the includer defined it before this header: the host test defines it
+// to a checker of every limb against the class, so the contracts are exercised and not only stated.
 #pragma once
 
 #include <stdint.h>
@@ -29,12 +33,20 @@
 #define FE_LOOP
 #endif
 
+#ifndef FE_AUDIT
+#define FE_AUDIT(site, fe, cls)
+#endif
+
 namespace efl {
 namespace fe {
 
 struct Fe {
   uint32_t v[10];
 };
+
+// what FE_AUDIT is handed: the class a site states, and the site
+enum AuditClass { kTight, kLoose };
+enum AuditSite { kMulF, kMulG, kSqrF, kA24F, kSubF, kSubG, kCarryH, kAuditSites };
 
 // the clamped scalar as the ladder reads it: bit t is (w[t / 32] >> (t % 32)) & 1
 struct Scalar {
@@ -84,6 +96,8 @@ FE_FN void add(Fe& h, const Fe& f, const Fe& g) {
 
 // h = f - g + 2 p, limb by limb: f tight, g tight (every limb of g is at most 2 p's) -> loose
 FE_FN void sub(Fe& h, const Fe& f, const Fe& g) {
+  FE_AUDIT(kSubF, f, kTight);
+  FE_AUDIT(kSubG, g, kTight);
   h.v[0] = f.v[0] + 0x7ffffdau - g.v[0];
   FE_UNROLL
   for (int i = 1; i < 10; ++i) h.v[i] = f.v[i] + ((i & 1) ? 0x3fffffeu : 0x7fffffeu) - g.v[i];
@@ -99,10 +113,16 @@ FE_FN void cswap(Fe& f, Fe& g, uint32_t mask) {
   }
 }
 
-// the columns t (each below 2^63) to tight limbs. Two interleaved chains (0 -> 5 and 4 -> 9 -> 0 -> 1)
-// so that no carry waits for nine others: 0, 4, 1, 5, 2, 6, 3, 7, 4, 8, 9 (times 19 into limb 0), 0.
-// Limbs 0 and 4 are carried twice; limb 1 ends below 2^25 + 2^16, limb 5 below 2^25 + 2^11, the rest
+// the columns t to tight limbs. Two interleaved chains (0 -> 5 and 4 -> 9 -> 0 -> 1) so that no
+// carry waits for nine others: 0, 4, 1, 5, 2, 6, 3, 7, 4, 8, 9 (times 19 into limb 0), 0. Limbs 0
+// and 4 are carried twice; limbs 1 and 5 take a last carry after they were masked, the rest end
 // below 2^bits.
+// Precondition: the columns mul, sqr and mul_a24 form of loose operands, each below 2^62.2 and
+// column 9 (whose carry is the one multiplied by 19) below 2^57.5. For those limb 1 ends at most
+// 2^25 + 1711 and limb 5 at most 2^25 + 1062, both below 2^25 + 2^11. Columns below 2^62 each
+// would still end tight (limb 1 at most 2^25 + 38,912); columns merely below 2^63 would not: limb 1
+// can reach 2^25 + 77,823, past the tight 2^25 + 2^16, and limb 5 2^25 + 4,095. The exact-integer
+// model of tests/x25519_domain.py proves these figures.
 FE_FN void carry(Fe& h, uint64_t t[10]) {
   uint64_t c;
 #define FE_CARRY(i, j, m)             \
@@ -115,11 +135,14 @@ FE_FN void carry(Fe& h, uint64_t t[10]) {
 #undef FE_CARRY
   FE_UNROLL
   for (int i = 0; i < 10; ++i) h.v[i] = (uint32_t)t[i];
+  FE_AUDIT(kCarryH, h, kTight);
 }
 
 // h = f g: loose operands -> tight. 100 products; limb products whose positions are both odd count
 // twice (25.5-bit radix) and those that wrap past limb 9 count 19 times.
 FE_FN void mul(Fe& h, const Fe& f, const Fe& g) {
+  FE_AUDIT(kMulF, f, kLoose);
+  FE_AUDIT(kMulG, g, kLoose);
   uint32_t g19[10], f2[10];
   FE_UNROLL
   for (int i = 0; i < 10; ++i) {
@@ -143,6 +166,7 @@ FE_FN void mul(Fe& h, const Fe& f, const Fe& g) {
 
 // h = f^2: loose -> tight. 55 products: the cross products are doubled in the left operand.
 FE_FN void sqr(Fe& h, const Fe& f) {
+  FE_AUDIT(kSqrF, f, kLoose);
   uint32_t f19[10];
   FE_UNROLL
   for (int i = 0; i < 10; ++i) f19[i] = 19u * f.v[i];
@@ -163,6 +187,7 @@ FE_FN void sqr(Fe& h, const Fe& f) {
 
 // h = 121665 f (a24 = (486662 - 2) / 4): loose -> tight
 FE_FN void mul_a24(Fe& h, const Fe& f) {
+  FE_AUDIT(kA24F, f, kLoose);
   uint64_t t[10];
   FE_UNROLL
   for (int i = 0; i < 10; ++i) t[i] = (uint64_t)f.v[i] * 121665u;
