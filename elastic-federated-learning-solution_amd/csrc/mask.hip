@@ -359,17 +359,29 @@ __global__ __launch_bounds__(kBlock) void k_mask_rows(const float* __restrict__ 
 // r = sqrt(-2 log u1), (f0, f1) = r (sin v1, cos v1). Element i takes normal i % 4 of block
 // ctr0 + i / 4, as the uniform masks do.
 //
-// logf / sqrtf over the arguments Box-Muller reaches: box_muller_math.h.
-__device__ __forceinline__ void box_muller(uint32_t x0, uint32_t x1, float& f0, float& f1) {
+// The radius over the arguments Box-Muller reaches (log_unit, radius_unit): box_muller_math.h.
+//
+// Both forms below (one pair; 2 NB pairs stage by stage) start from the Philox words, so that
+// efl_dp_box_muller can put chosen words through the very functions k_dp_noise runs
+// (tests/test_box_muller_domain_gpu.py walks all 2^23 radii and angles that way). KEEP hands out the
+// stage values of a pair; the production instances (KEEP = false) compute nothing for it.
+struct bm_stages { float r, sn, cs; };
+
+template <bool KEEP = false>
+__device__ __forceinline__ void box_muller(uint32_t x0, uint32_t x1, float& f0, float& f1,
+                                           bm_stages* st = nullptr) {
   const float u1 = u01(x0);
   const float v1 = efl_box_muller_angle(u01(x1));   // float(2 pi (double) u), no doubles
   // both arms computed and one selected: a branch around the logarithm costs more than it saves
-  const float rr = sqrt_normal(-2.0f * log_unit(fmaxf(u1, 1.0e-7f)));
+  float tl;
+  const float lg = log_unit(fmaxf(u1, 1.0e-7f), tl);
+  const float rr = radius_unit(lg, tl);
   const float r = u1 < 1.0e-7f ? __uint_as_float(kRClampBits) : rr;
   float sn, cs;
   efl_sincos_angle(v1, &sn, &cs);   // v1 in [0, 2 pi]: <= 1 ulp of the rounded sin / cos (sincos_angle.h)
   f0 = sn * r;
   f1 = cs * r;
+  if constexpr (KEEP) *st = bm_stages{r, sn, cs};
 }
 
 __device__ __forceinline__ void normal4(uint64_t seed, uint64_t blk, float (&z)[4]) {
@@ -383,29 +395,29 @@ __device__ __forceinline__ void normal4(uint64_t seed, uint64_t blk, float (&z)[
 // stage by stage across the 2 NB Box-Muller pairs (Philox rounds, logarithms, square roots, angles)
 // so that every stage has 2 NB independent chains to fill the transcendental and compare hazards
 // with (round 5: before, each pair ran to the end on its own, with s_nop between dependent steps).
-template <int NB>
-__device__ __forceinline__ void normals(uint64_t seed, uint64_t blk0, uint64_t stride, float (&z)[NB][4]) {
+//
+// box_muller_staged: the stages after the Philox rounds, pair p on the words c[p / 2][2 (p % 2)]
+// (radius) and c[p / 2][2 (p % 2) + 1] (angle). `words(c)` fills the NB blocks: the Philox rounds
+// in production, loads of chosen words in efl_dp_box_muller. It is a callable and not an array
+// argument so that the words are made inside this function, as they were before it was split from
+// normals<NB>: k_dp_noise then compiles to the same instructions (with an array argument the
+// compiler no longer narrowed the last Philox round of the words whose low 23 bits alone are used;
+// with a callable that captures by reference the NB = 1 instances changed). DESIGN.md §5c.
+template <int NB, bool KEEP = false, class WORDS>
+__device__ __forceinline__ void box_muller_staged(WORDS words, float (&z)[NB][4], bm_stages* st = nullptr) {
   constexpr int P = 2 * NB;
   uint32_t c[NB][4];
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    const uint64_t blk = blk0 + (uint64_t)b * stride;
-    c[b][0] = (uint32_t)blk;
-    c[b][1] = (uint32_t)(blk >> 32);
-    c[b][2] = 0u;
-    c[b][3] = 0u;
-  }
-  pl::philox_n<NB>(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-  float u1[P], v1[P], r[P], sn[P], cs[P];
+  words(c);
+  float u1[P], v1[P], r[P], tl[P], sn[P], cs[P];
 #pragma unroll
   for (int p = 0; p < P; ++p) {
     u1[p] = u01(c[p >> 1][(p & 1) * 2]);
     v1[p] = efl_box_muller_angle(u01(c[p >> 1][(p & 1) * 2 + 1]));
   }
 #pragma unroll
-  for (int p = 0; p < P; ++p) r[p] = -2.0f * log_unit(fmaxf(u1[p], 1.0e-7f));
+  for (int p = 0; p < P; ++p) r[p] = log_unit(fmaxf(u1[p], 1.0e-7f), tl[p]);
 #pragma unroll
-  for (int p = 0; p < P; ++p) r[p] = sqrt_normal(r[p]);
+  for (int p = 0; p < P; ++p) r[p] = radius_unit(r[p], tl[p]);
 #pragma unroll
   for (int p = 0; p < P; ++p) r[p] = u1[p] < 1.0e-7f ? __uint_as_float(kRClampBits) : r[p];
 #pragma unroll
@@ -415,6 +427,27 @@ __device__ __forceinline__ void normals(uint64_t seed, uint64_t blk0, uint64_t s
     z[p >> 1][(p & 1) * 2] = sn[p] * r[p];
     z[p >> 1][(p & 1) * 2 + 1] = cs[p] * r[p];
   }
+  if constexpr (KEEP) {
+#pragma unroll
+    for (int p = 0; p < P; ++p) st[p] = bm_stages{r[p], sn[p], cs[p]};
+  }
+}
+
+template <int NB>
+__device__ __forceinline__ void normals(uint64_t seed, uint64_t blk0, uint64_t stride, float (&z)[NB][4]) {
+  box_muller_staged<NB>(
+      [=](uint32_t (&c)[NB][4]) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+          const uint64_t blk = blk0 + (uint64_t)b * stride;
+          c[b][0] = (uint32_t)blk;
+          c[b][1] = (uint32_t)(blk >> 32);
+          c[b][2] = 0u;
+          c[b][3] = 0u;
+        }
+        pl::philox_n<NB>(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+      },
+      z);
 }
 
 // MODE 0, ElementWiseGaussianSumQuery.add_noise (dp_optimizer.py:70-71): v + normal * v * sigma;
@@ -467,6 +500,60 @@ __global__ __launch_bounds__(kBlock) void k_dp_noise(const float* x, float* o,  
     } else {
       for (int j = 0; j < 4 && i0 + j < n; ++j) o[i0 + j] = dp_one<MODE, POW2>(x[i0 + j], z[j], sigma, div);
     }
+  }
+}
+
+// Test support (efl_dp_box_muller): Box-Muller of given word pairs through the functions above.
+// Pair i is (x0[i], x1[i]); r / sn / cs (each may be null) take its stage values, z0 / z1 the normals.
+__device__ __forceinline__ void bm_store(long long i, const bm_stages& st, float f0, float f1, float* r, float* sn,
+                                         float* cs, float* z0, float* z1) {
+  if (r) r[i] = st.r;
+  if (sn) sn[i] = st.sn;
+  if (cs) cs[i] = st.cs;
+  z0[i] = f0;
+  z1[i] = f1;
+}
+
+__device__ __forceinline__ void bm_pair(const uint32_t* x0, const uint32_t* x1, long long i, float* r, float* sn,
+                                        float* cs, float* z0, float* z1) {
+  bm_stages st;
+  float f0, f1;
+  box_muller<true>(x0[i], x1[i], f0, f1, &st);
+  bm_store(i, st, f0, f1, r, sn, cs, z0, z1);
+}
+
+// NB = 0: one pair per lane through box_muller (normal4's and the tail's code). NB in {1, 2, 4}: a
+// lane takes 2 NB consecutive pairs through box_muller_staged together, as normals<NB> does after
+// its Philox rounds; the lane of a ragged last group runs its pairs one by one, as k_dp_noise's tail.
+template <int NB>
+__global__ __launch_bounds__(kBlock) void k_box_muller(const uint32_t* __restrict__ x0, const uint32_t* __restrict__ x1,
+                                                       long long n, float* r, float* sn, float* cs, float* z0,
+                                                       float* z1) {
+  const long long g = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if constexpr (NB == 0) {
+    if (g < n) bm_pair(x0, x1, g, r, sn, cs, z0, z1);
+  } else {
+    constexpr int P = 2 * NB;
+    const long long i0 = g * P;
+    if (i0 >= n) return;
+    if (i0 + P <= n) {
+      float z[NB][4];
+      bm_stages st[P];
+      box_muller_staged<NB, true>(
+          [=](uint32_t (&c)[NB][4]) {
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+              c[p >> 1][(p & 1) * 2] = x0[i0 + p];
+              c[p >> 1][(p & 1) * 2 + 1] = x1[i0 + p];
+            }
+          },
+          z, st);
+#pragma unroll
+      for (int p = 0; p < P; ++p)
+        bm_store(i0 + p, st[p], z[p >> 1][(p & 1) * 2], z[p >> 1][(p & 1) * 2 + 1], r, sn, cs, z0, z1);
+      return;
+    }
+    for (long long i = i0; i < n; ++i) bm_pair(x0, x1, i, r, sn, cs, z0, z1);
   }
 }
 
@@ -738,4 +825,29 @@ EFL_API int efl_dp_noise(const float* x, float* out, int64_t n, int mode, float 
   else if (pow2) launch_dp<1, true>(nb, lanes, x, out, n, seed, ctr0, sigma, d, s);
   else launch_dp<1, false>(nb, lanes, x, out, n, seed, ctr0, sigma, d, s);
   return hip_status(hipGetLastError(), "efl_dp_noise");
+}
+
+EFL_API int efl_dp_box_muller(const uint32_t* x0, const uint32_t* x1, int64_t n, int nb, float* r, float* sn,
+                              float* cs, float* z0, float* z1, void* stream) {
+  if (n < 0) { set_error("negative element count"); return EFL_E_INVALID_ARGUMENT; }
+  if (nb != 0 && nb != 1 && nb != 2 && nb != 4) {
+    set_error("efl_dp_box_muller: nb must be 0 (per pair) or 1, 2, 4 (staged), got %d", nb);
+    return EFL_E_INVALID_ARGUMENT;
+  }
+  if (n == 0) return EFL_OK;
+  if (!x0 || !x1 || !z0 || !z1) { set_error("null buffer"); return EFL_E_INVALID_ARGUMENT; }
+  if (!aligned(x0, 4) || !aligned(x1, 4) || !aligned(r, 4) || !aligned(sn, 4) || !aligned(cs, 4) || !aligned(z0, 4) ||
+      !aligned(z1, 4)) {
+    set_error("efl_dp_box_muller: buffers must be 4-byte aligned");
+    return EFL_E_INVALID_ARGUMENT;
+  }
+  const long long lanes = nb == 0 ? n : (n + 2 * nb - 1) / (2 * nb);
+  if (!lanes_ok(lanes)) { set_error("efl_dp_box_muller: too many pairs"); return EFL_E_INVALID_ARGUMENT; }
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned grid = grid_for(lanes);
+  if (nb == 0) k_box_muller<0><<<grid, kBlock, 0, s>>>(x0, x1, n, r, sn, cs, z0, z1);
+  else if (nb == 1) k_box_muller<1><<<grid, kBlock, 0, s>>>(x0, x1, n, r, sn, cs, z0, z1);
+  else if (nb == 2) k_box_muller<2><<<grid, kBlock, 0, s>>>(x0, x1, n, r, sn, cs, z0, z1);
+  else k_box_muller<4><<<grid, kBlock, 0, s>>>(x0, x1, n, r, sn, cs, z0, z1);
+  return hip_status(hipGetLastError(), "efl_dp_box_muller");
 }

@@ -19,6 +19,11 @@
 // with gcc (-ffp-contract=off, the kernel file's own `fp contract(off)`; every fused step is an
 // explicit fma, so host and device round identically) and compares every reachable angle and every
 // 61st float of [0, 2 pi] with the correctly rounded sin / cos (double libm, rounded to float).
+// That host and device round identically is checked on the device on every run of the suite:
+// tests/test_box_muller_domain_gpu.py puts all 2^23 angle words through the kernel's functions
+// (efl_dp_box_muller) and compares sn and cs bit for bit with this header's host build, by the chunk
+// digests of tests/golden/box_muller_domain.json (tests/test_box_muller_domain_host.py regenerates
+// them with gcc). tools/dp_fastmath_check.hip made the same comparison once, in round 5.
 #pragma once
 
 #ifdef __HIPCC__

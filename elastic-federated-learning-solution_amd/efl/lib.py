@@ -47,6 +47,8 @@ _SIGS = {
     "efl_ss_mask_rows": ([_vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_uint64, ctypes.c_uint64, _vp], _i32),
     "efl_dp_noise": ([_vp, _vp, _i64, _i32, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _vp],
                      _i32),
+    # test support: Box-Muller of chosen words through efl_dp_noise's device functions
+    "efl_dp_box_muller": ([_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
     # RSA blind-signature PSI (efl.psi; include/efl_hip.h efl_rsa_*): contexts and info structs as void*
     "efl_rsa_ctx_create": ([_vp], _i32),
     "efl_rsa_ctx_destroy": ([_vp], _i32),

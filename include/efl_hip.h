@@ -666,6 +666,15 @@ int efl_ss_mask_rows(const float* b, float* send, float* keep0, float* keep1, in
  * device buffers; out may equal x. */
 int efl_dp_noise(const float* x, float* out, int64_t n, int mode, float sigma, float divisor, uint64_t seed,
                  uint64_t ctr0, void* stream);
+/* Test support, for the domain tests (tests/test_box_muller_domain_gpu.py): Box-Muller of chosen
+ * Philox words through the device functions efl_dp_noise's kernel runs, which cannot be steered from
+ * a seed. Pair i takes x0[i] (the radius's uniform) and x1[i] (the angle's); z0[i] = r sin v,
+ * z1[i] = r cos v, and r / sn / cs (each may be null) take the stage values r, sin v, cos v. nb = 0:
+ * the per-pair code (the kernel's tail); nb = 1, 2, 4: the staged code, a lane taking 2 nb consecutive
+ * pairs through the stages together (a ragged last group pair by pair). Device buffers of n elements,
+ * 4-byte aligned; plain stores. */
+int efl_dp_box_muller(const uint32_t* x0, const uint32_t* x1, int64_t n, int nb, float* r, float* sn,
+                      float* cs, float* z0, float* z1, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,8 +17,9 @@ DP-SGD noise (efls-train/python/efl/privacy/dp_optimizer.py:60-73; tensorflow_pr
 GaussianSumQuery): tf.random.normal is TF's NormalDistribution over the same Philox words --
 Box-Muller on word pairs (0, 1), (2, 3) of each block (BoxMullerFloat: u1 = max(U(x0), 1e-7),
 v1 = float(2 pi * U(x1)) in double, r = sqrt(-2 log u1), (r sin v1, r cos v1)). log/sin/cos here are
-float64 rounded to float32 (correctly rounded); the kernels use the device's logf / sincosf, so the
-normals agree to a few ulp, not bit for bit (the tests state the tolerance). Parity with the
+float64 rounded to float32 (correctly rounded); the kernels use their own float log, root, sin and
+cos, so the normals agree to a few ulp, not bit for bit (the tests state the tolerance, and
+tests/test_box_muller_domain_gpu.py holds it over every uniform through normal_from_words). Parity with the
 reference is statistical only: its stream is unseeded.
 """
 import numpy as np
@@ -90,22 +91,33 @@ def mask_rows(b: np.ndarray, seed: int, ctr0: int):
     return send, (half + f).astype(np.float32), (f_odd + f_even).astype(np.float32)
 
 
+def word_uniform(w) -> np.ndarray:
+    """TF's Uint32ToFloat of Philox words: the low 23 bits under exponent 127, minus 1.0."""
+    w = np.asarray(w, dtype=np.uint32)
+    bits = (np.uint32(0x3F800000) | (w & np.uint32(0x7FFFFF))).view(np.float32)
+    return (bits - np.float32(1.0)).astype(np.float32)
+
+
+def normal_from_words(x0, x1):
+    """TF's BoxMullerFloat of the word pairs (x0[i], x1[i]): (r, sn, cs, z0, z1) float32 arrays, the
+    radius sqrt(-2 log max(U(x0), 1e-7)), sin and cos of the angle float(2 pi U(x1)), and the two
+    normals sn r and cs r. Every step is the float64 function rounded to float32."""
+    u1 = np.maximum(word_uniform(x0), np.float32(1.0e-7)).astype(np.float32)
+    v1 = (2.0 * np.pi * word_uniform(x1).astype(np.float64)).astype(np.float32)
+    lg = np.log(u1.astype(np.float64)).astype(np.float32)
+    r = np.sqrt((np.float32(-2.0) * lg).astype(np.float32).astype(np.float64)).astype(np.float32)
+    sn = np.sin(v1.astype(np.float64)).astype(np.float32)
+    cs = np.cos(v1.astype(np.float64)).astype(np.float32)
+    return r, sn, cs, (sn * r).astype(np.float32), (cs * r).astype(np.float32)
+
+
 def normal(seed: int, ctr0: int, n: int) -> np.ndarray:
     """N(0, 1) float32 for elements 0..n-1 of one call (TF's Box-Muller over Philox word pairs)."""
     nb = (n + 3) // 4
     w = philox_blocks(seed, ctr0, nb)
-    u = (np.uint32(0x3F800000) | (w & np.uint32(0x7FFFFF))).view(np.float32) - np.float32(1.0)
-    u = u.astype(np.float32)
     out = np.empty((nb, 4), np.float32)
     for a, b in ((0, 1), (2, 3)):
-        u1 = np.maximum(u[:, a], np.float32(1.0e-7)).astype(np.float32)
-        v1 = (2.0 * np.pi * u[:, b].astype(np.float64)).astype(np.float32)
-        lg = np.log(u1.astype(np.float64)).astype(np.float32)
-        r = np.sqrt((np.float32(-2.0) * lg).astype(np.float32).astype(np.float64)).astype(np.float32)
-        sn = np.sin(v1.astype(np.float64)).astype(np.float32)
-        cs = np.cos(v1.astype(np.float64)).astype(np.float32)
-        out[:, a] = sn * r
-        out[:, b] = cs * r
+        out[:, a], out[:, b] = normal_from_words(w[:, a], w[:, b])[3:]
     return out.reshape(-1)[:n]
 
 
