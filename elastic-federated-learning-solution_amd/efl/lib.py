@@ -73,6 +73,16 @@ _SIGS = {
                          _i32),
     "efl_idset_find": ([_vp, _i64, _i32, _vp, _vp, _i64, ctypes.c_uint64, _vp, _vp], _i32),
     "efl_idset_rehash": ([_vp, _i32, _vp, _i64, _vp, _i64, ctypes.c_uint64, _vp], _i32),
+    # the bucket hash and partition (efl.psi.bucket, efl.psi.check_sum); the *_host ones take host memory
+    "efl_mmh3_hash_host": ([ctypes.c_char_p, _i64, ctypes.c_uint32], ctypes.c_int32),
+    "efl_mmh3_hash_rows_host": ([_vp, _vp, _i64, ctypes.c_uint32, _vp], _i32),
+    "efl_mmh3_checksum_host": ([ctypes.c_int32, _vp, _vp, _i64], ctypes.c_int32),
+    "efl_mmh3_hash": ([_vp, _vp, _i64, ctypes.c_uint32, _vp, _vp], _i32),
+    "efl_bucket_ids": ([_vp, _i64, _i64, ctypes.c_int32, _vp, _vp], _i32),
+    "efl_bucket_scratch_bytes": ([_i64, _i32], _i64),
+    "efl_bucket_partition": ([_vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp], _i32),
+    "efl_strings_gather_scratch_bytes": ([_i64], _i64),
+    "efl_strings_gather": ([_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp], _i32),
 }
 for _name, (_args, _ret) in _SIGS.items():
     _f = getattr(_lib, _name)

@@ -5,7 +5,10 @@ a signature (rsa_cipher) and the PKCS#1 key reader / writer) and ECDH over curve
 EccSigner, and batched X25519 over uint8 rows in ecc_cipher); and what the signed IDs go into: IdStore
 (id_store.py), the reference's SampleKvStore as a hash table in device memory, and the transport-free
 joins on top of it (ecdh_join.py: EcdhJoinServer, EcdhJoinClient; rsa_join.py: RsaJoinServer,
-RsaJoinClient)."""
+RsaJoinClient); and what the reference's jobs put around a join: the bucket hash that keys every record
+to one join per bucket (bucket.py: mmh3_hash, DefaultKeySelector, get_local_bucket_id, partition),
+the CheckSum that closes a bucket's join (check_sum.py) and the joins run bucket by bucket
+(bucketed_join.py: BucketedJoinServer, BucketedJoinClient)."""
 from efl.psi import pkcs1
 from efl.psi import rsa_cipher
 from efl.psi import rsa_signer
@@ -20,7 +23,14 @@ from efl.psi.ecc_signer import EccSigner
 from efl.psi.id_store import IdStore
 from efl.psi.ecdh_join import EcdhJoinServer, EcdhJoinClient
 from efl.psi.rsa_join import RsaJoinServer, RsaJoinClient
+from efl.psi import bucket
+from efl.psi import bucketed_join
+from efl.psi.bucket import mmh3_hash, mmh3_hash_rows, get_local_bucket_id, DefaultKeySelector, partition
+from efl.psi.check_sum import CheckSum, check_sum
+from efl.psi.bucketed_join import BucketedJoinServer, BucketedJoinClient
 
 __all__ = ["RsaSigner", "ServerRsaSigner", "ClientRsaSigner", "RsaKey", "EccSigner", "IdStore", "EcdhJoinServer",
            "EcdhJoinClient", "RsaJoinServer", "RsaJoinClient", "pkcs1", "rsa_cipher", "rsa_signer", "ecc_cipher",
-           "ecc_signer", "id_store", "ecdh_join", "rsa_join"]
+           "ecc_signer", "id_store", "ecdh_join", "rsa_join", "bucket", "bucketed_join", "mmh3_hash",
+           "mmh3_hash_rows", "get_local_bucket_id", "DefaultKeySelector", "partition", "CheckSum", "check_sum",
+           "BucketedJoinServer", "BucketedJoinClient"]

@@ -15,8 +15,9 @@ h(x) = sha256("curve25519" + x):
 
 Here both stores are efl.psi.IdStore tables on the device, every signature is one batched X25519
 launch (efl.psi.ecc_cipher), and a block is a `uint8` [n, 32] tensor that never leaves the device
-between the two halves. Left to the service around it: gRPC, CheckSum and the bucket hash, Flink,
-LevelDB.
+between the two halves. This is one bucket's join: the bucket hash, the join run bucket by bucket and
+the CheckSum that closes each are efl.psi.bucket, efl.psi.bucketed_join and efl.psi.check_sum
+(DESIGN.md §5h). Left to the service around it: gRPC, Flink, LevelDB.
 """
 from __future__ import annotations
 

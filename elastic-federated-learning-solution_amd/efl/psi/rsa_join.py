@@ -15,8 +15,9 @@ key, h(x) = sha256(str(x)) and H the one-way hash of a signature's decimal text:
 Here the store is an efl.psi.IdStore(8) on the device, a signed ID is a row of a `uint8` [n, 8] tensor
 (rsa_cipher.oneway_rows; rsa_cipher.oneway_text gives the reference's byte string), blinded hashes
 and signatures are `int32` [n, words] rows, and nothing leaves the device between the steps except
-the existence flags. Left to the service around it: IsReady / FinishJoin, CheckSum and the bucket
-hash, gRPC, Flink, LevelDB.
+the existence flags. This is one bucket's join: the bucket hash, the join run bucket by bucket,
+CheckSum and FinishJoin are efl.psi.bucket, efl.psi.bucketed_join and efl.psi.check_sum (DESIGN.md
+§5h). Left to the service around it: IsReady, gRPC, Flink, LevelDB.
 """
 from __future__ import annotations
 

@@ -616,6 +616,67 @@ int efl_idset_find(const uint8_t* rows, int64_t n, int width, const uint8_t* key
 int efl_idset_rehash(const uint8_t* keys, int width, const int64_t* size, int64_t size_bound, uint32_t* slots,
                      int64_t capacity, uint64_t seed, void* stream);
 
+/* ---- Bucket hash and partition (efl.psi.bucket, efl.psi.check_sum) ------------------------------
+ * Replaces the per-record `mmh3.hash(id) % bucket_num` by which both parties of the reference key
+ * their records to one join server per bucket (efls-data/xfl/data/functions.py:37-46, DefaultKeySelector
+ * and get_local_bucket_id) and the Flink key_by that regroups them, and gives the CheckSum that closes
+ * a bucket's join (xfl/data/check_sum.py): MurmurHash3_x86_32, Python's `%` of its signed result, a
+ * stable counting sort of the rows by bucket and the rows' strings regrouped in that order
+ * (csrc/mmh3.h, csrc/bucket.hip). Strings are packed as efl_sha256_fdh takes them: string i is
+ * chars[offsets[i] .. offsets[i+1]), offsets int64 [n + 1], 8-byte aligned. Every buffer is the
+ * caller's, in device memory (the *_host functions: host memory). n == 0 is a no-op, before anything
+ * else is looked at; a negative count, a null buffer, a misaligned buffer, a bucket count, modulus or
+ * divisor out of range and a scratch that is too small are INVALID_ARGUMENT before any HIP call; more
+ * than 2^31 - 2 rows are RESOURCE_EXHAUSTED. Stream-ordered, no host synchronisation, no allocation;
+ * no kernel waits for another lane, and a call's output is the same bytes on every run. */
+/* mmh3.hash(data, seed) on the HOST: the signed 32-bit MurmurHash3_x86_32 of len bytes of any
+ * alignment. 0 for a negative len or a null pointer with len > 0. */
+int32_t efl_mmh3_hash_host(const void* data, int64_t len, uint32_t seed);
+/* out[i] = mmh3.hash(string i, seed) on the HOST, one thread (a caller with several threads gives
+ * each a range of rows: chars + 0, offsets + first, out + first). */
+int efl_mmh3_hash_rows_host(const char* chars, const int64_t* offsets, int64_t n, uint32_t seed, int32_t* out);
+/* CheckSum.add_list on the HOST: for each of the n strings in turn
+ * cur = mmh3.hash(str(cur).encode() + string, 0), str() with a '-' for a negative cur; the last cur
+ * (cur itself for n <= 0 or a null buffer). The chain is serial by definition. */
+int32_t efl_mmh3_checksum_host(int32_t cur, const char* chars, const int64_t* offsets, int64_t n);
+/* out[i] (int32 [n]) = mmh3.hash(string i, seed), signed. One string per lane; strings start at any
+ * byte offset and have any length. */
+int efl_mmh3_hash(const char* chars, const int64_t* offsets, int64_t n, uint32_t seed, int32_t* out,
+                  void* stream);
+/* out[i] = (hash[i] % modulus) // divisor with Python's % (in [0, modulus) for a negative hash too),
+ * 1 <= divisor <= modulus <= 2^31 - 1. DefaultKeySelector(bucket_num, c).get_key is
+ * (bucket_num * c, c); get_local_bucket_id(key, c) is (c, 1). out may be hash. */
+int efl_bucket_ids(const int32_t* hash, int64_t n, int64_t modulus, int32_t divisor, int32_t* out,
+                   void* stream);
+/* Bytes of efl_bucket_partition's scratch (0 for n <= 0, n > 2^31 - 2 or buckets outside 1 .. 4096):
+ * one word per bucket, and one more, for every 2,048 rows, and the scan's per-block sums. */
+int64_t efl_bucket_scratch_bytes(int64_t n, int buckets);
+/* A stable counting sort of the rows by bucket[i] (int32 [n]), 1 <= buckets <= 4096:
+ *   order  int64 [n]            the row indices grouped by bucket, ascending inside a bucket: the
+ *                               order in which a Flink key_by hands a subtask its records
+ *   starts int64 [buckets + 1]  the exclusive scan of the bucket sizes: bucket b is
+ *                               order[starts[b] .. starts[b+1])
+ * A row whose bucket[i] is outside [0, buckets) belongs to no bucket: such rows follow the last
+ * bucket in `order`, ascending, from order[starts[buckets]] on, so starts[buckets] is the number of
+ * rows that have a bucket (n when all have) and every entry of `order` is written. `scratch` is
+ * scratch_len >= efl_bucket_scratch_bytes(n, buckets) bytes, 8-byte aligned, free again once the
+ * call's work on `stream` is done. Five launches: the per-tile histogram, the exclusive scan of the
+ * tile-by-bucket counts in bucket-major order (three), the scatter. */
+int efl_bucket_partition(const int32_t* bucket, int64_t n, int buckets, int64_t* order, int64_t* starts,
+                         void* scratch, int64_t scratch_len, void* stream);
+/* Bytes of efl_strings_gather's scratch (0 for n <= 0 or n > 2^31 - 2). */
+int64_t efl_strings_gather_scratch_bytes(int64_t n);
+/* The strings in `order` (int64 [n]), packed back to back: string i of the result is string order[i]
+ * of the input and out_offsets (int64 [n + 1]) its offsets from 0 (an order entry outside [0, n)
+ * gives an empty string). out_chars holds the listed strings' bytes: as many as the input's strings
+ * have when `order` is a permutation, as efl_bucket_partition's is; the caller sizes it. After
+ * efl_bucket_partition bucket b's strings are out_offsets[starts[b] .. starts[b+1]] over the one
+ * out_chars buffer, a slice efl_x25519_hash and efl_sha256_fdh take as it is. Four launches: the
+ * partition's scan over the lengths (three), the copy. out_chars must not overlap chars. */
+int efl_strings_gather(const char* chars, const int64_t* offsets, const int64_t* order, int64_t n,
+                       char* out_chars, int64_t* out_offsets, void* scratch, int64_t scratch_len,
+                       void* stream);
+
 /* ---- Key generation, HOST memory (GeneratePaillierKeypairOp, paillier.cc:833-904) ------------
  * The reference's keygen is a CPU op over GMP (mpz_probab_prime_p in find_prime, :851-863;
  * mpz_powm for hs, :884-888). These two are its arithmetic, on host buffers of little-endian
