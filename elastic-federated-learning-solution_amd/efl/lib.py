@@ -83,6 +83,14 @@ _SIGS = {
     "efl_bucket_partition": ([_vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp], _i32),
     "efl_strings_gather_scratch_bytes": ([_i64], _i64),
     "efl_strings_gather": ([_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp], _i32),
+    # the sort join's order (efl.psi.strsort): a segmented string sort, search and run heads
+    "efl_strings_sort_scratch_bytes": ([_i64], _i64),
+    "efl_strings_sort": ([_vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp], _i32),
+    "efl_strings_search": ([_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp], _i32),
+    "efl_strings_run_heads": ([_vp, _vp, _vp, _i64, _vp, _vp], _i32),
+    "efl_strings_sort_host": ([_vp, _vp, _vp, _i64, _i32, _vp], _i32),
+    "efl_strings_search_host": ([_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp], _i32),
+    "efl_strings_run_heads_host": ([_vp, _vp, _vp, _i64, _vp], _i32),
 }
 for _name, (_args, _ret) in _SIGS.items():
     _f = getattr(_lib, _name)

@@ -677,6 +677,49 @@ int efl_strings_gather(const char* chars, const int64_t* offsets, const int64_t*
                        char* out_chars, int64_t* out_offsets, void* scratch, int64_t scratch_len,
                        void* stream);
 
+/* ---- The sort join's order: a segmented byte-string sort, search and run heads (efl.psi.strsort) ----
+ * Replaces what the reference's default data-join does to its record keys hash_col + b'#' + sort_col
+ * (efls-data/xfl/data/utils.py:63-69): sorted(keys, key=cmp_to_key(record_cmp)) on the client
+ * (xfl/data/functions.py:49-60,261) and the dict lookup of SampleKvStore.exists on the server
+ * (xfl/service/data_join_server.py:86-102), over strings of any length packed as above (csrc/strsort.h,
+ * csrc/strsort.hip). The key order of EFL_SORT_BYTES is Python's `bytes` order (unsigned bytes, the
+ * first difference decides, a proper prefix is smaller); EFL_SORT_RECORD is record_cmp: field 1 (the
+ * bytes between the first and the second '#', or to the end), then field 0 (the bytes before the
+ * first '#'), each in `bytes` order; a key without '#' has an empty field 1. The same rules as the
+ * bucket functions: caller-owned buffers, n == 0 a no-op, bad arguments INVALID_ARGUMENT before any
+ * HIP call, more than 2^31 - 2 rows RESOURCE_EXHAUSTED, stream-ordered, no host synchronisation, no
+ * allocation, no kernel waits for another lane, the same bytes on every run. */
+#define EFL_SORT_BYTES 0
+#define EFL_SORT_RECORD 1
+/* Bytes of efl_strings_sort's scratch (0 for n <= 0 or n > 2^31 - 2): 48 per row, two buffers of
+ * 16-byte entries and the field extents. */
+int64_t efl_strings_sort_scratch_bytes(int64_t n);
+/* order (int64 [n]) <- the permutation of 0 .. n-1 that is ascending in (segment[i] as signed int32,
+ * key order of `mode`, i): a stable sort, one correct output for every input. segment (int32 [n]) may
+ * be null: one segment. `scratch` is scratch_len >= efl_strings_sort_scratch_bytes(n) bytes, 16-byte
+ * aligned, free again once the call's work on `stream` is done. 2 + ceil(log2(ceil(n / 2048)))
+ * launches: the entries, the tile sort, the rank merges. */
+int efl_strings_sort(const char* chars, const int64_t* offsets, const int32_t* segment, int64_t n, int mode,
+                     int64_t* order, void* scratch, int64_t scratch_len, void* stream);
+/* out[j] (int64 [nq]) <- the table row of the first row in t_order whose string equals query j, or
+ * -1; t_order is an EFL_SORT_BYTES order of the m table strings without segments, so that is the
+ * lowest row index among equal strings. m == 0 (the table buffers may be null): all -1. One lane per
+ * query, one launch. */
+int efl_strings_search(const char* t_chars, const int64_t* t_offsets, const int64_t* t_order, int64_t m,
+                       const char* q_chars, const int64_t* q_offsets, int64_t nq, int64_t* out, void* stream);
+/* heads[k] (uint8 [n]) <- 1 when k == 0 or the strings of rows order[k] and order[k-1] differ in full
+ * bytes, length included, else 0. One launch. */
+int efl_strings_run_heads(const char* chars, const int64_t* offsets, const int64_t* order, int64_t n,
+                          uint8_t* heads, void* stream);
+/* The same three on the HOST, one thread, host buffers, no scratch (the sort is std::stable_sort with
+ * the comparators of csrc/strsort.h). */
+int efl_strings_sort_host(const char* chars, const int64_t* offsets, const int32_t* segment, int64_t n, int mode,
+                          int64_t* order);
+int efl_strings_search_host(const char* t_chars, const int64_t* t_offsets, const int64_t* t_order, int64_t m,
+                            const char* q_chars, const int64_t* q_offsets, int64_t nq, int64_t* out);
+int efl_strings_run_heads_host(const char* chars, const int64_t* offsets, const int64_t* order, int64_t n,
+                               uint8_t* heads);
+
 /* ---- Key generation, HOST memory (GeneratePaillierKeypairOp, paillier.cc:833-904) ------------
  * The reference's keygen is a CPU op over GMP (mpz_probab_prime_p in find_prime, :851-863;
  * mpz_powm for hs, :884-888). These two are its arithmetic, on host buffers of little-endian
