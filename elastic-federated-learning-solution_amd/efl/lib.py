@@ -45,6 +45,8 @@ _SIGS = {
     "efl_ss_noise": ([_vp, _vp, _vp, _i64, _i32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_float, _vp], _i32),
     "efl_ss_mask_cols": ([_vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_uint64, ctypes.c_uint64, _vp], _i32),
     "efl_ss_mask_rows": ([_vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_uint64, ctypes.c_uint64, _vp], _i32),
+    # the products around the masks in one launch: terms is an array of SsTerm (below)
+    "efl_ss_products": ([_vp, _i32, _vp, _i64, _i64, _i64, _i32, _vp], _i32),
     "efl_dp_noise": ([_vp, _vp, _i64, _i32, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _vp],
                      _i32),
     # test support: Box-Muller of chosen words through efl_dp_noise's device functions
@@ -96,6 +98,16 @@ for _name, (_args, _ret) in _SIGS.items():
     _f = getattr(_lib, _name)
     _f.argtypes = _args
     _f.restype = _ret
+
+SS_MAX_TERMS = 8
+
+
+class SsTerm(ctypes.Structure):
+    """efl_ss_term (include/efl_hip.h): one signed product A [rows, k] @ B [k, cols] of
+    efl_ss_products, each operand a device pointer with a row and a column stride in elements."""
+    _fields_ = [("a", _vp), ("a_rs", _i64), ("a_cs", _i64), ("b", _vp), ("b_rs", _i64), ("b_cs", _i64),
+                ("k", _i64), ("sign", ctypes.c_int32)]
+
 
 # TensorFlow DataType numbers (types.proto), as used by the C ABI and the wire format.
 DT_FLOAT, DT_DOUBLE, DT_INT32, DT_INT16, DT_INT8, DT_STRING, DT_INT64 = 1, 2, 3, 5, 6, 7, 9

@@ -8,7 +8,10 @@ Reference: efls-train/python/efl/privacy/secret_sharing.py
 Every per-element mask runs in one HIP kernel of libefl_hip.so (csrc/mask.hip: efl_ss_noise,
 efl_ss_mask_cols, efl_ss_mask_rows) that reads the tensor once and writes every share the
 protocol needs, instead of TF's chain of uniform/mul/slice/add/concat ops. The products
-(`(a - e) @ b1 + ...`) are plain library GEMMs (torch.matmul -> hipBLASLt). No CPU fallback.
+(`(a - e) @ b1 + ...`) are library GEMMs (torch.matmul -> hipBLASLt) by default; with
+`product="fused"` (or `set_product("fused")`) all products of a `_matmul` are one launch of
+efl_ss_products (csrc/ssgemm.hip), an fp32-MFMA GEMM over the concatenated inner dimension that
+reads the slices and transposes of the received tensor as strided views. No CPU fallback.
 
 Randomness. The reference's `tf.random.uniform` is unseeded; here the uniform is the same
 construction (Philox4x32-10 + Uint32ToFloat) from a per-process `NoiseStream`: a 64-bit key drawn
@@ -139,6 +142,89 @@ def mask_rows(b, stream=None):
     return lib.back(send, home), lib.back(k0, home), lib.back(k1, home)
 
 
+PRODUCTS = ("library", "fused")
+_product = "library"
+
+
+@exporter.export("secret_sharing.set_product")
+def set_product(name: str) -> None:
+    """The process default of the `product` keyword of matmul / Dense / dense: "library" (one
+    torch.matmul per product, the default) or "fused" (one efl_ss_products launch per _matmul)."""
+    global _product
+    _product = _resolve_product(name)
+
+
+def _resolve_product(product):
+    product = _product if product is None else product
+    if product not in PRODUCTS:
+        raise ValueError(f"secret_sharing: product must be one of {PRODUCTS}, got {product!r}")
+    return product
+
+
+def _view_stride(t, d):
+    """Stride of dimension d for the kernel: a dimension of one element never steps, so any
+    positive number serves (torch reports arbitrary strides there)."""
+    return int(t.stride(d)) if t.shape[d] > 1 else 1
+
+
+@exporter.export("secret_sharing.fused_products")
+def fused_products(terms, out=None, tile=None):
+    """sum_t sign_t * A_t @ B_t in one launch (efl_ss_products, fp32 MFMA, fp32 accumulation in
+    the order of `terms`). terms: up to 8 of (A, B) or (A, B, sign), A [R, K_t] and B [K_t, N]
+    float32 tensors on one ROCm device, any 2-D views with positive strides (transposes and slices
+    are read in place, never copied), sign +1 or -1. Returns the [R, N] result: `out` if given (a
+    float32 [R, N] view with unit column stride that overlaps no operand; with no terms it is
+    zeroed), a new tensor otherwise. tile: None lets the library pick its 32x32 or 64x64
+    workgroup tile, 32 or 64 names one."""
+    terms = list(terms)
+    if len(terms) > lib.SS_MAX_TERMS:
+        raise errors.InvalidArgumentError(f"fused_products: at most {lib.SS_MAX_TERMS} terms, got {len(terms)}")
+    if not terms and out is None:
+        raise errors.InvalidArgumentError("fused_products: no terms and no out= to take the shape from")
+    ops = []
+    for i, term in enumerate(terms):
+        if len(term) not in (2, 3):
+            raise errors.InvalidArgumentError(f"fused_products: term {i} is not (A, B) or (A, B, sign)")
+        sign = term[2] if len(term) == 3 else 1
+        if sign not in (1, -1):
+            raise errors.InvalidArgumentError(f"fused_products: term {i}: sign must be +1 or -1, got {sign!r}")
+        for t in term[:2]:
+            if not isinstance(t, torch.Tensor) or t.dim() != 2:
+                raise errors.InvalidArgumentError(f"fused_products: term {i}: operands must be 2-D tensors")
+            if t.dtype != torch.float32:
+                raise errors.InvalidArgumentError(f"fused_products: term {i}: operands are float32, got {t.dtype}")
+        A, B = term[0].detach(), term[1].detach()
+        if A.shape[1] != B.shape[0]:
+            raise errors.InvalidArgumentError(
+                f"fused_products: term {i}: inner dimensions differ, {tuple(A.shape)} @ {tuple(B.shape)}")
+        ops.append((A, B, int(sign)))
+    R, N = (ops[0][0].shape[0], ops[0][1].shape[1]) if ops else tuple(out.shape)
+    for i, (A, B, _) in enumerate(ops):
+        if A.shape[0] != R or B.shape[1] != N:
+            raise errors.InvalidArgumentError(
+                f"fused_products: term {i} is {tuple(A.shape)} @ {tuple(B.shape)}, the result is [{R}, {N}]")
+    tensors = [t for A, B, _ in ops for t in (A, B)] + ([out] if out is not None else [])
+    dev = tensors[0].device
+    if dev.type != "cuda" or any(t.device != dev for t in tensors):
+        raise errors.InvalidArgumentError("fused_products: operands and out must be on one ROCm device")
+    if out is None:
+        out = torch.empty((R, N), dtype=torch.float32, device=dev)
+    elif (out.dtype != torch.float32 or tuple(out.shape) != (R, N) or out.requires_grad
+          or (N > 1 and out.stride(1) != 1)):
+        raise errors.InvalidArgumentError(
+            f"fused_products: out must be a float32 [{R}, {N}] view with unit column stride")
+    arr = (lib.SsTerm * lib.SS_MAX_TERMS)()
+    for rec, (A, B, sign) in zip(arr, ops):
+        if min(_view_stride(A, 0), _view_stride(A, 1), _view_stride(B, 0), _view_stride(B, 1)) < 1:
+            raise errors.InvalidArgumentError("fused_products: operand strides must be positive (no expanded views)")
+        rec.a, rec.a_rs, rec.a_cs = A.data_ptr(), _view_stride(A, 0), _view_stride(A, 1)
+        rec.b, rec.b_rs, rec.b_cs = B.data_ptr(), _view_stride(B, 0), _view_stride(B, 1)
+        rec.k, rec.sign = A.shape[1], sign
+    lib.check(lib.raw().efl_ss_products(arr, len(ops), out.data_ptr(), int(out.stride(0)) if R > 1 else max(N, 1),
+                                        R, N, int(tile or 0), lib.stream_handle(dev)))
+    return out
+
+
 def _shape(m):
     if isinstance(m, torch.Tensor):
         return tuple(int(s) for s in m.shape)
@@ -150,11 +236,13 @@ def _recv(communicator, name, shape, like):
     return t.to(like.device)
 
 
-def _matmul(a, b, communicator, name, mode):
+def _matmul(a, b, communicator, name, mode, product="library"):
     """secret_sharing.py:30-77. Mode A: this party holds a, `b` is the peer's shape. Mode B: holds
     b, `a` is the peer's shape. Mode C: holds both; the result summed over the two parties is
-    (a_0 + a_1) @ (b_0 + b_1)."""
+    (a_0 + a_1) @ (b_0 + b_1). product "fused": the products of the mode are one fused_products
+    call over views of the held and received tensors."""
     mode = Mode(mode) if not isinstance(mode, Mode) else mode
+    fused = _resolve_product(product) == "fused"
     if mode == Mode.A:
         K, N = _shape(b)
         send_t, a_minus_e, eo_minus_ee = mask_cols(a)
@@ -162,6 +250,8 @@ def _matmul(a, b, communicator, name, mode):
         b1_and_f1 = _recv(communicator, name + "_b1_and_f1", (K * 3 // 2, N), send_t)
         b1, f1 = b1_and_f1[:K], b1_and_f1[K:]
         h.result()
+        if fused:
+            return fused_products([(a_minus_e, b1), (eo_minus_ee, f1)])
         return a_minus_e @ b1 + eo_minus_ee @ f1
     if mode == Mode.B:
         R, C = _shape(a)
@@ -170,13 +260,15 @@ def _matmul(a, b, communicator, name, mode):
         a1_and_e1 = _recv(communicator, name + "_a1_and_e1", (R, C * 3 // 2), send_t)
         a1, e1 = a1_and_e1[:, :C], a1_and_e1[:, C:]
         h.result()
+        if fused:
+            return fused_products([(a1, half_plus_f), (e1, fo_plus_fe, -1)])
         return a1 @ half_plus_f - e1 @ fo_plus_fe
     if mode == Mode.C:
         if a.dtype != b.dtype:
             raise TypeError("The dtypes of a and b must be the same.")
         R, C = a.shape
         N = b.shape[1]
-        z = a @ b
+        z = None if fused else a @ b
         a_send, a_minus_e, eo_minus_ee = mask_cols(a)
         b_send, half_plus_f, fo_plus_fe = mask_rows(b)
         send_t = torch.cat([a_send, b_send.t()], dim=0)
@@ -186,14 +278,18 @@ def _matmul(a, b, communicator, name, mode):
         ra1, re1 = a1_e1[:, :C], a1_e1[:, C:]
         rb1, rf1 = b1_f1[:C], b1_f1[C:]
         h.result()
+        if fused:
+            return fused_products([(a, b), (a_minus_e, rb1), (eo_minus_ee, rf1), (ra1, half_plus_f),
+                                   (re1, fo_plus_fe, -1)])
         z1 = a_minus_e @ rb1 + eo_minus_ee @ rf1
         z2 = ra1 @ half_plus_f - re1 @ fo_plus_fe
         return z + z1 + z2
     raise ValueError(str(mode) + ": No such mode.")
 
 
-def _grad_c(a, b, dy, communicator, name, combine_gradients):
-    """The mode-C backward of matmul (secret_sharing.py:83-106)."""
+def _grad_c(a, b, dy, communicator, name, combine_gradients, product="library"):
+    """The mode-C backward of matmul (secret_sharing.py:83-106); its matmuls take the forward's
+    `product`."""
     if combine_gradients:
         B, U = dy.shape
         R, C = a.shape
@@ -202,23 +298,23 @@ def _grad_c(a, b, dy, communicator, name, combine_gradients):
                            torch.cat([torch.zeros_like(b), a.t()], dim=1)], dim=0)
         bt_dy = torch.cat([torch.cat([b.t(), z((U, U))], dim=1),
                            torch.cat([torch.zeros_like(a), dy], dim=1)], dim=0)
-        da_db = _matmul(dy_at, bt_dy, communicator, name + "_gradient", Mode.C)
+        da_db = _matmul(dy_at, bt_dy, communicator, name + "_gradient", Mode.C, product)
         return da_db[:R, :C], da_db[-C:, -U:]
-    da = _matmul(dy, b.t().contiguous(), communicator, name + "_da", Mode.C)
-    db = _matmul(a.t().contiguous(), dy, communicator, name + "_db", Mode.C)
+    da = _matmul(dy, b.t().contiguous(), communicator, name + "_da", Mode.C, product)
+    db = _matmul(a.t().contiguous(), dy, communicator, name + "_db", Mode.C, product)
     return da, db
 
 
 class _SSMatmul(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, a, b, communicator, name, mode, combine_gradients):
+    def forward(ctx, a, b, communicator, name, mode, combine_gradients, product):
         ctx.save_for_backward(a, b)
-        ctx.args = (communicator, name, mode, combine_gradients)
-        return _matmul(a, b, communicator, name, mode)
+        ctx.args = (communicator, name, mode, combine_gradients, product)
+        return _matmul(a, b, communicator, name, mode, product)
 
     @staticmethod
     def backward(ctx, dy):
-        communicator, name, mode, combine_gradients = ctx.args
+        communicator, name, mode, combine_gradients, product = ctx.args
         if mode == Mode.A:
             raise ValueError("Please switch from mode A to mode C, because mode A is equivalent to mode C "
                              "when the gradients need to be computed.")
@@ -226,23 +322,26 @@ class _SSMatmul(torch.autograd.Function):
             raise ValueError("Please switch from mode B to mode C, because mode B is equivalent to mode C "
                              "when the gradients need to be computed.")
         a, b = ctx.saved_tensors
-        da, db = _grad_c(a, b, dy.contiguous(), communicator, name, combine_gradients)
-        return da, db, None, None, None, None
+        da, db = _grad_c(a, b, dy.contiguous(), communicator, name, combine_gradients, product)
+        return da, db, None, None, None, None, None
 
 
 @exporter.export("secret_sharing.matmul")
-def matmul(a, b, communicator, name, mode, combine_gradients=False):
-    """secret_sharing.py:80-109: the secret-shared product, differentiable in mode C."""
+def matmul(a, b, communicator, name, mode, combine_gradients=False, product=None):
+    """secret_sharing.py:80-109: the secret-shared product, differentiable in mode C. product:
+    "library" or "fused" (see fused_products), None for the process default (set_product); the
+    backward's matmuls use the forward's."""
     mode = Mode(mode) if not isinstance(mode, Mode) else mode
+    product = _resolve_product(product)
     if mode == Mode.C and (a.requires_grad or b.requires_grad) and torch.is_grad_enabled():
-        return _SSMatmul.apply(a, b, communicator, name, mode, combine_gradients)
+        return _SSMatmul.apply(a, b, communicator, name, mode, combine_gradients, product)
     if mode == Mode.C:
-        return _matmul(a, b, communicator, name, mode)
+        return _matmul(a, b, communicator, name, mode, product)
     if mode == Mode.A and isinstance(a, torch.Tensor) and a.requires_grad and torch.is_grad_enabled():
-        return _ModeAB.apply(a, communicator, name, mode, _shape(b))
+        return _ModeAB.apply(a, communicator, name, mode, _shape(b), product)
     if mode == Mode.B and isinstance(b, torch.Tensor) and b.requires_grad and torch.is_grad_enabled():
-        return _ModeAB.apply(b, communicator, name, mode, _shape(a))
-    return _matmul(a, b, communicator, name, mode)
+        return _ModeAB.apply(b, communicator, name, mode, _shape(a), product)
+    return _matmul(a, b, communicator, name, mode, product)
 
 
 matmul.Mode = Mode   # the reference exports the enum as secret_sharing.matmul.Mode
@@ -252,11 +351,11 @@ class _ModeAB(torch.autograd.Function):
     """Modes A and B forward; their backward raises as the reference's grad does (:84-87)."""
 
     @staticmethod
-    def forward(ctx, held, communicator, name, mode, peer_shape):
+    def forward(ctx, held, communicator, name, mode, peer_shape, product):
         ctx.mode = mode
         if mode == Mode.A:
-            return _matmul(held, peer_shape, communicator, name, mode)
-        return _matmul(peer_shape, held, communicator, name, mode)
+            return _matmul(held, peer_shape, communicator, name, mode, product)
+        return _matmul(peer_shape, held, communicator, name, mode, product)
 
     @staticmethod
     def backward(ctx, dy):
@@ -323,8 +422,9 @@ class SecretSharingDense(torch.nn.Module):
     layer; `kernel_initializer(tensor)` fills it in place (default glorot-uniform as TF's)."""
 
     def __init__(self, communicator, prefix, units, noise_divisor=None, combine_gradients=False,
-                 use_bias=True, kernel_initializer=None, bias_initializer=None, **kwargs):
+                 use_bias=True, kernel_initializer=None, bias_initializer=None, product=None, **kwargs):
         super().__init__()
+        self._product = product
         self._communicator = communicator
         self._prefix = prefix
         self.units = int(units)
@@ -365,7 +465,7 @@ class SecretSharingDense(torch.nn.Module):
             h.result()
             kernel = (kernel + (kept - kernel.detach()) + peer) / 2
         outputs = matmul(inputs, kernel, self._communicator, self._prefix, Mode.C,
-                         combine_gradients=self._combine_gradients)
+                         combine_gradients=self._combine_gradients, product=self._product)
         if self.use_bias:
             outputs = outputs + self.bias
         return outputs
@@ -375,9 +475,10 @@ class SecretSharingDense(torch.nn.Module):
 
 
 @exporter.export("secret_sharing.dense")
-def dense(inputs, communicator, prefix, units, noise_divisor=None, combine_gradients=False, **kwargs):
+def dense(inputs, communicator, prefix, units, noise_divisor=None, combine_gradients=False, product=None,
+          **kwargs):
     """secret_sharing.py:152-155. Returns (outputs, layer), as efl.paillier.*.dense do: a torch
     tensor cannot carry the layer's variables the way a TF graph collection does."""
     layer = SecretSharingDense(communicator, prefix, units, noise_divisor=noise_divisor,
-                               combine_gradients=combine_gradients, **kwargs)
+                               combine_gradients=combine_gradients, product=product, **kwargs)
     return layer(inputs), layer

@@ -760,6 +760,32 @@ int efl_ss_mask_cols(const float* a, float* send, float* keep0, float* keep1, in
 int efl_ss_mask_rows(const float* b, float* send, float* keep0, float* keep1, int64_t rows,
                      int64_t cols, uint64_t seed, uint64_t ctr0, void* stream);
 
+/* The products around the masks (_matmul :36-41, :48-53, :62-77) in one launch:
+ *   z[rows, cols] = sum over t < count of sign_t * A_t[rows, k_t] @ B_t[k_t, cols],
+ * fp32 MFMA with fp32 accumulation, the terms accumulated in the order given (csrc/ssgemm.hip).
+ * A mode-C forward is one call of five terms. Each operand is a view of device memory: a pointer
+ * and a row and a column stride in elements, both >= 1 and otherwise arbitrary, so a transposed or
+ * sliced tensor is read where it lies (loads coalesce when either stride is 1). k_t >= 0; a term
+ * with k_t == 0 contributes nothing and its pointers are not looked at. z has column stride 1 and
+ * row stride z_row_stride >= cols. rows == 0 or cols == 0 is a no-op; count == 0 writes zeros.
+ * tile: 0 picks the workgroup tile from rows and cols (32x32, one wave, when that holds the whole
+ * result; 64x64, four waves, otherwise); 32 or 64 names one. The result does not depend on anything
+ * but the inputs and the tile. Stream-ordered: no allocation, no device-side table (the terms travel as kernel
+ * arguments) and no synchronisation. EFL_E_INVALID_ARGUMENT, before any HIP call, for: count
+ * outside 0 .. EFL_SS_MAX_TERMS, a dimension outside 0 .. 2^31 - 1, a sign other than +1 / -1, a
+ * null z or operand, a stride < 1, z_row_stride < cols, and a z that overlaps an operand. */
+#define EFL_SS_MAX_TERMS 8
+typedef struct efl_ss_term {
+  const float* a;          /* A_t [rows, k]: element (i, j) at a[i * a_rs + j * a_cs] */
+  int64_t a_rs, a_cs;
+  const float* b;          /* B_t [k, cols]: element (i, j) at b[i * b_rs + j * b_cs] */
+  int64_t b_rs, b_cs;
+  int64_t k;
+  int32_t sign;            /* +1 or -1 */
+} efl_ss_term;
+int efl_ss_products(const efl_ss_term* terms, int count, float* z, int64_t z_row_stride, int64_t rows,
+                    int64_t cols, int tile, void* stream);
+
 /* ---- DP-SGD noise ---------------------------------------------------------
  * The noise step of efls-train/python/efl/privacy/dp_optimizer.py's DP optimisers over a summed
  * gradient x (n floats), then safe_normalize's division (:210-214), in one pass:
