@@ -26,6 +26,7 @@
 #include "box_muller_math.h"
 #include "group_div.h"
 #include "sincos_angle.h"
+#include "dp_normal.h"
 
 // Every product and sum rounds on its own, as TF's separate ops (and numpy in the oracle) do:
 // hipcc contracts a*b+c into one FMA by default, which changes the last bit.
@@ -56,10 +57,6 @@ __device__ __forceinline__ void stv(T* p, T v) {
   } else {
     *p = v;
   }
-}
-
-__device__ __forceinline__ float u01(uint32_t w) {
-  return __uint_as_float(0x3f800000u | (w & 0x7fffffu)) - 1.0f;
 }
 
 __device__ __forceinline__ void draw4(uint64_t seed, uint64_t blk, float (&u)[4]) {
@@ -361,36 +358,12 @@ __global__ __launch_bounds__(kBlock) void k_mask_rows(const float* __restrict__ 
 //
 // The radius over the arguments Box-Muller reaches (log_unit, radius_unit): box_muller_math.h.
 //
-// Both forms below (one pair; 2 NB pairs stage by stage) start from the Philox words, so that
-// efl_dp_box_muller can put chosen words through the very functions k_dp_noise runs
-// (tests/test_box_muller_domain_gpu.py walks all 2^23 radii and angles that way). KEEP hands out the
-// stage values of a pair; the production instances (KEEP = false) compute nothing for it.
-struct bm_stages { float r, sn, cs; };
-
-template <bool KEEP = false>
-__device__ __forceinline__ void box_muller(uint32_t x0, uint32_t x1, float& f0, float& f1,
-                                           bm_stages* st = nullptr) {
-  const float u1 = u01(x0);
-  const float v1 = efl_box_muller_angle(u01(x1));   // float(2 pi (double) u), no doubles
-  // both arms computed and one selected: a branch around the logarithm costs more than it saves
-  float tl;
-  const float lg = log_unit(fmaxf(u1, 1.0e-7f), tl);
-  const float rr = radius_unit(lg, tl);
-  const float r = u1 < 1.0e-7f ? __uint_as_float(kRClampBits) : rr;
-  float sn, cs;
-  efl_sincos_angle(v1, &sn, &cs);   // v1 in [0, 2 pi]: <= 1 ulp of the rounded sin / cos (sincos_angle.h)
-  f0 = sn * r;
-  f1 = cs * r;
-  if constexpr (KEEP) *st = bm_stages{r, sn, cs};
-}
-
-__device__ __forceinline__ void normal4(uint64_t seed, uint64_t blk, float (&z)[4]) {
-  uint32_t c[4] = {(uint32_t)blk, (uint32_t)(blk >> 32), 0u, 0u};
-  philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-  box_muller(c[0], c[1], z[0], z[1]);
-  box_muller(c[2], c[3], z[2], z[3]);
-}
-
+// Both forms (one pair: box_muller and normal4 in dp_normal.h, shared with csrc/dpclip.hip; 2 NB
+// pairs stage by stage, below) start from the Philox words, so that efl_dp_box_muller can put chosen
+// words through the very functions k_dp_noise runs (tests/test_box_muller_domain_gpu.py walks all
+// 2^23 radii and angles that way). KEEP hands out the stage values of a pair; the production
+// instances (KEEP = false) compute nothing for it. dp_one, the noise and the division: dp_normal.h.
+//
 // The normals of NB blocks (blk0, blk0 + stride, ...), the same values as normal4 on each, computed
 // stage by stage across the 2 NB Box-Muller pairs (Philox rounds, logarithms, square roots, angles)
 // so that every stage has 2 NB independent chains to fill the transcendental and compare hazards
@@ -448,17 +421,6 @@ __device__ __forceinline__ void normals(uint64_t seed, uint64_t blk0, uint64_t s
         pl::philox_n<NB>(c, (uint32_t)seed, (uint32_t)(seed >> 32));
       },
       z);
-}
-
-// MODE 0, ElementWiseGaussianSumQuery.add_noise (dp_optimizer.py:70-71): v + normal * v * sigma;
-// MODE 1, GaussianSumQuery (tensorflow_privacy 0.3.0, TF 1.x branch): v + (normal * stddev + 0);
-// then safe_normalize (dp_optimizer.py:210-214): / num_microbatches. Each op rounds on its own.
-// POW2: the divisor is a power of two and `div` holds its reciprocal: x * 2^-k is the correctly
-// rounded x / 2^k (the same exact real, one rounding), without the IEEE division sequence.
-template <int MODE, bool POW2>
-__device__ __forceinline__ float dp_one(float v, float z, float sigma, float div) {
-  const float n = MODE == 0 ? (z * v) * sigma : z * sigma + 0.0f;
-  return POW2 ? (v + n) * div : (v + n) / div;
 }
 
 // One lane owns NB Philox blocks (4 elements each) kBlock lanes apart, so a wave's accesses stay
@@ -815,10 +777,8 @@ EFL_API int efl_dp_noise(const float* x, float* out, int64_t n, int mode, float 
   const long long lanes = (n + 3) / 4;
   if (!lanes_ok(lanes)) { set_error("efl_dp_noise: tensor too large"); return EFL_E_INVALID_ARGUMENT; }
   hipStream_t s = (hipStream_t)stream;
-  int ex = 0;
-  const bool pow2 = std::isfinite(divisor) && std::frexp(std::fabs(divisor), &ex) == 0.5f &&
-                    std::isnormal(1.0f / divisor);
-  const float d = pow2 ? 1.0f / divisor : divisor;   // exact for a power of two with a normal reciprocal
+  float d;
+  const bool pow2 = dp_divisor(divisor, &d);   // exact for a power of two with a normal reciprocal
   const int nb = g_dp_blocks.load(std::memory_order_relaxed);
   if (mode == 0 && pow2) launch_dp<0, true>(nb, lanes, x, out, n, seed, ctr0, sigma, d, s);
   else if (mode == 0) launch_dp<0, false>(nb, lanes, x, out, n, seed, ctr0, sigma, d, s);

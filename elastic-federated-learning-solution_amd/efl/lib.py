@@ -51,6 +51,10 @@ _SIGS = {
                      _i32),
     # test support: Box-Muller of chosen words through efl_dp_noise's device functions
     "efl_dp_box_muller": ([_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp], _i32),
+    # a DP-SGD step's clip, sum, noise and average over stacked gradients: vars is a host array of DpVar
+    "efl_dp_clip_work_elems": ([_vp, _i64, _i64], _i64),
+    "efl_dp_clip_sum": ([_vp, _i64, _i64, _i32, ctypes.c_float, _i32, ctypes.c_float, ctypes.c_float,
+                         ctypes.c_uint64, _vp, _vp, _i64, _vp], _i32),
     # RSA blind-signature PSI (efl.psi; include/efl_hip.h efl_rsa_*): contexts and info structs as void*
     "efl_rsa_ctx_create": ([_vp], _i32),
     "efl_rsa_ctx_destroy": ([_vp], _i32),
@@ -107,6 +111,12 @@ class SsTerm(ctypes.Structure):
     efl_ss_products, each operand a device pointer with a row and a column stride in elements."""
     _fields_ = [("a", _vp), ("a_rs", _i64), ("a_cs", _i64), ("b", _vp), ("b_rs", _i64), ("b_cs", _i64),
                 ("k", _i64), ("sign", ctypes.c_int32)]
+
+
+class DpVar(ctypes.Structure):
+    """efl_dp_var (include/efl_hip.h): one variable of efl_dp_clip_sum's record, its stacked
+    microbatch gradients (row r at grads + r * row_stride) and its [numel] output."""
+    _fields_ = [("grads", _vp), ("out", _vp), ("numel", _i64), ("row_stride", _i64), ("ctr0", ctypes.c_uint64)]
 
 
 # TensorFlow DataType numbers (types.proto), as used by the C ABI and the wire format.

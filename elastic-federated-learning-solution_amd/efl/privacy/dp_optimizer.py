@@ -14,8 +14,17 @@ Reference: efls-train/python/efl/privacy/dp_optimizer.py
 
 The noise and the division run as ONE HIP kernel per variable (csrc/mask.hip efl_dp_noise: read the
 sum once, write the averaged noised gradient once) with TF's normal construction (Philox4x32-10,
-Box-Muller) from a per-process `NoiseStream`. The per-microbatch gradients are autograd's; the
-clip is a torch reduction. No CPU fallback: the kernel needs the GPU.
+Box-Muller) from a per-process `NoiseStream`. No CPU fallback: the kernel needs the GPU.
+
+The per-microbatch gradients come one of two ways (`microbatch_gradients=`, process default by
+`set_microbatch_gradients`). "loop", the default: one autograd.grad per microbatch, the clip a
+torch reduction and the sum a torch addition per variable, as the reference's loop. "batched": ONE
+autograd.grad with is_grads_batched=True gives every variable's gradients stacked as [rows, ...],
+and for float32 device records the norms, the clip scales, the row-ordered sum, the noise and the
+division are two or three HIP launches whatever the model (csrc/dpclip.hip efl_dp_clip_sum,
+`dp_clip_sum_noise`): the same sum as the loop's given the same scales, the scales from a double
+accumulation instead of float32 reductions. Custom queries and other dtypes take
+`_SumQuery.accumulate_batch`, the loop restated over the stack.
 
 Torch mapping. TF optimisers get their variables at minimize time; torch ones at construction.
 These classes take either: `params` (as `params=`, or first positional with the DP arguments as
@@ -31,6 +40,8 @@ One reference quirk is kept: each microbatch's loss is `reduce_func(tf.gather(lo
 gradient is that of the row's SUM (TF differentiates a non-scalar loss as its sum).
 """
 from __future__ import annotations
+
+import ctypes
 
 import torch
 
@@ -72,6 +83,96 @@ def dp_noise(x: torch.Tensor, mode: int, sigma: float, divisor: float = 1.0, str
     return lib.back(out, home)
 
 
+MICROBATCH_GRADIENTS = ("loop", "batched")
+_microbatch_gradients = "loop"
+
+
+@exporter.export("privacy.set_microbatch_gradients")
+def set_microbatch_gradients(name: str) -> None:
+    """The process default of the DP optimisers' `microbatch_gradients` keyword: "loop" (one
+    autograd.grad and one torch clip-and-add per microbatch, the default) or "batched" (one batched
+    autograd.grad, then efl_dp_clip_sum over the stacked gradients)."""
+    global _microbatch_gradients
+    _microbatch_gradients = _resolve_microbatch_gradients(name)
+
+
+def _resolve_microbatch_gradients(name):
+    name = _microbatch_gradients if name is None else name
+    if name not in MICROBATCH_GRADIENTS:
+        raise ValueError(f"microbatch_gradients must be one of {MICROBATCH_GRADIENTS}, got {name!r}")
+    return name
+
+
+def _rows_view(t):
+    """(view, numel, row_stride) of a [rows, ...] float32 device tensor as efl_dp_clip_sum reads it:
+    a view whose rows are contiguous and at least numel apart is taken as it is (a padded row
+    stride included), anything else is made contiguous."""
+    rows = t.shape[0]
+    numel = t[0].numel() if rows else 0
+    if rows and numel and not (t[0].is_contiguous() and (rows == 1 or t.stride(0) >= numel)):
+        t = t.contiguous()
+    return t, numel, int(t.stride(0)) if rows > 1 and numel else numel
+
+
+@exporter.export("privacy.dp_clip_sum_noise")
+def dp_clip_sum_noise(stacked, l2_norm_clip, mode: int, sigma: float, divisor: float = 1.0,
+                      stream: NoiseStream | None = None, scales=None, return_scales: bool = False):
+    """efl_dp_clip_sum over a record's stacked microbatch gradients: `stacked` is a list of
+    [rows, ...] float32 device tensors, one per variable. Returns, per variable,
+    noise(sum over rows, in row order, of g_r * scale_r) / divisor with efl_dp_noise's `mode`, `sigma`
+    and `divisor`; the noise positions are taken from `stream` (default: the process's) as the loop
+    path takes them, one take(numel) per variable, in order.
+    scale_r: 1 with l2_norm_clip None and no `scales`; `scales` ([rows] float32) when given; else
+    clip * min(1 / ||g_r||, 1 / clip), the norm over all variables of row r accumulated in double.
+    return_scales: also return the [rows] scales used (ones when there are none)."""
+    stacked = [lib.as_tensor(t).detach() for t in stacked]
+    if not stacked:
+        return ([], None) if return_scales else []
+    dev, rows = stacked[0].device, stacked[0].shape[0] if stacked[0].dim() else 0
+    for t in stacked:
+        if t.dtype != torch.float32 or t.device != dev or dev.type != "cuda" or t.dim() < 1 or t.shape[0] != rows:
+            raise errors.InvalidArgumentError(
+                "dp_clip_sum_noise: every variable is a [rows, ...] float32 tensor on one ROCm device")
+    if rows < 1:
+        raise errors.InvalidArgumentError("dp_clip_sum_noise: no rows")
+    views = [_rows_view(t) for t in stacked]
+    outs = lib._carve([t[0] for t in stacked], torch.float32, dev)
+    arr = (lib.DpVar * len(views))()
+    seed = None
+    for rec, (t, numel, stride), out in zip(arr, views, outs):
+        seed, ctr0 = (stream or _stream).take(numel)
+        rec.grads, rec.out, rec.numel, rec.row_stride, rec.ctr0 = t.data_ptr(), out.data_ptr(), numel, stride, ctr0
+    clip_mode = 2 if scales is not None else 0 if l2_norm_clip is None else 1
+    work, work_elems = None, 0
+    if clip_mode == 2:
+        scales = lib.as_tensor(scales).detach().to(dev, torch.float32).contiguous()
+        if scales.shape != (rows,):
+            raise errors.InvalidArgumentError(f"dp_clip_sum_noise: scales must be [{rows}]")
+    elif clip_mode == 1:
+        numels = (ctypes.c_int64 * len(views))(*[v[1] for v in views])
+        work_elems = lib.raw().efl_dp_clip_work_elems(numels, len(views), rows)
+        if work_elems < 0:
+            lib.check(int(work_elems))
+        work = torch.empty(max(work_elems, 1), dtype=torch.float64, device=dev)
+        scales = torch.empty(rows, dtype=torch.float32, device=dev)
+    lib.check(lib.raw().efl_dp_clip_sum(arr, len(views), rows, clip_mode, float(l2_norm_clip or 0.0), int(mode),
+                                        float(sigma), float(divisor), seed,
+                                        None if scales is None else scales.data_ptr(),
+                                        None if work is None else work.data_ptr(), work_elems,
+                                        lib.stream_handle(dev)))
+    if return_scales:
+        return outs, torch.ones(rows, device=dev) if scales is None else scales
+    return outs
+
+
+def _fusable(query, cls, stacked):
+    """efl_dp_clip_sum does exactly the stock query's clip, sum and noise: only an instance of the
+    stock class itself over a float32 device stack takes it. A subclass (its own clip, noise, ledger
+    or state) keeps the restated loop, so what it overrides is honoured as under "loop"."""
+    return type(query) is cls and bool(stacked) and all(t.dtype == torch.float32 and t.is_cuda and t.dim() >= 1 and t.shape[0] > 0
+                                 for t in stacked)
+
+
 def _zeros_like(t):
     return torch.zeros_like(t)
 
@@ -95,8 +196,21 @@ class _SumQuery:
         rec = self.preprocess_record(params, record)
         return [s + r for s, r in zip(sample_state, rec)]
 
+    def accumulate_batch(self, params, stacked):
+        """The sample state of a record whose microbatch gradients lie stacked as [rows, ...] per
+        variable: accumulate_record row by row, the loop restated over the stack."""
+        state = self.initial_sample_state([t[0] for t in stacked])
+        for i in range(stacked[0].shape[0]):
+            state = self.accumulate_record(params, state, [t[i] for t in stacked])
+        return state
+
     def get_noised_result(self, sample_state, global_state, divisor: float = 1.0):
         raise NotImplementedError
+
+    def get_noised_batch(self, params, stacked, global_state, divisor: float = 1.0):
+        """get_noised_result of accumulate_batch; the Gaussian queries fuse the two into
+        efl_dp_clip_sum for float32 device stacks."""
+        return self.get_noised_result(self.accumulate_batch(params, stacked), global_state, divisor)
 
 
 @exporter.export("privacy.GaussianSumQuery")
@@ -122,6 +236,11 @@ class GaussianSumQuery(_SumQuery):
     def get_noised_result(self, sample_state, global_state, divisor: float = 1.0):
         return [dp_noise(v, 1, self._stddev, divisor) for v in sample_state], global_state
 
+    def get_noised_batch(self, params, stacked, global_state, divisor: float = 1.0):
+        if not _fusable(self, GaussianSumQuery, stacked):
+            return super().get_noised_batch(params, stacked, global_state, divisor)
+        return dp_clip_sum_noise(stacked, params, 1, self._stddev, divisor), global_state
+
 
 @exporter.export("privacy.ElementWiseGaussianSumQuery")
 class ElementWiseGaussianSumQuery(_SumQuery):
@@ -132,6 +251,11 @@ class ElementWiseGaussianSumQuery(_SumQuery):
 
     def get_noised_result(self, sample_state, global_state, divisor: float = 1.0):
         return [dp_noise(v, 0, self._noise_multiplier, divisor) for v in sample_state], global_state
+
+    def get_noised_batch(self, params, stacked, global_state, divisor: float = 1.0):
+        if not _fusable(self, ElementWiseGaussianSumQuery, stacked):
+            return super().get_noised_batch(params, stacked, global_state, divisor)
+        return dp_clip_sum_noise(stacked, None, 0, self._noise_multiplier, divisor), global_state
 
 
 _DEFAULT_OPT_CONFIG = {"REDUCE": "mean"}
@@ -185,7 +309,10 @@ def make_optimizer_class(cls):
     class DPOptimizerClass(cls):
         def __init__(self, *args, **kwargs):
             """(dp_sum_query, num_microbatches=None, unroll_microbatches=False, [params], **opt
-            kwargs), or torch style (params, dp_sum_query=..., ...)."""
+            kwargs), or torch style (params, dp_sum_query=..., ...). microbatch_gradients= "loop" /
+            "batched" (keyword only; None: the process default, set_microbatch_gradients)."""
+            self._microbatch_gradients = kwargs.pop("microbatch_gradients", None)
+            _resolve_microbatch_gradients(self._microbatch_gradients)
             if "learning_rate" in kwargs:
                 kwargs["lr"] = kwargs.pop("learning_rate")
             lead = _as_params(args[0]) if args else None
@@ -202,7 +329,7 @@ def make_optimizer_class(cls):
             self._dp_sum_query = dp_sum_query
             self._num_microbatches = num_microbatches
             self._global_state = dp_sum_query.initial_global_state()
-            self._unroll_microbatches = unroll_microbatches   # microbatches always run as a Python loop
+            self._unroll_microbatches = unroll_microbatches   # kept for the signature: see microbatch_gradients
             self._was_compute_gradients_called = False
             self._opt_args, self._opt_kwargs = args, kwargs
             self._built = False
@@ -236,6 +363,11 @@ def make_optimizer_class(cls):
             loss = loss.reshape(nm, -1)
             grad_loss = None if grad_loss is None else grad_loss.reshape(nm, -1)
             params = self._dp_sum_query.derive_sample_params(self._global_state)
+            if _resolve_microbatch_gradients(self._microbatch_gradients) == "batched":
+                stacked = self._stacked_gradients(loss, var_list, grad_loss, reduce_func)
+                final, self._global_state = self._dp_sum_query.get_noised_batch(params, stacked, self._global_state,
+                                                                                divisor=float(nm))
+                return list(zip(final, var_list))
             state = self._dp_sum_query.initial_sample_state([v.detach() for v in var_list])
             for i in range(nm):
                 row = loss[i]
@@ -249,6 +381,30 @@ def make_optimizer_class(cls):
             final, self._global_state = self._dp_sum_query.get_noised_result(state, self._global_state,
                                                                              divisor=float(nm))
             return list(zip(final, var_list))
+
+        @staticmethod
+        def _stacked_gradients(loss, var_list, grad_loss, reduce_func):
+            """Every microbatch's gradients from ONE backward: [nm, *v.shape] per variable, row i the
+            gradient the loop takes of row i of the [nm, k] loss, up to the summation order of torch's
+            batched backward kernels (equal bits for the linear model of the GPU test; a CPU
+            convolution backward has given other last bits). An unused variable gives zeros."""
+            nm = loss.shape[0]
+            if callable(reduce_func):
+                loss = torch.stack([reduce_func(loss[i:i + 1], 0) for i in range(nm)])
+            go = torch.ones_like(loss) if grad_loss is None else grad_loss.reshape(loss.shape)
+            # E[i] selects row i: zero but for row i, which carries that row's grad_outputs
+            sel = torch.zeros((nm,) + tuple(loss.shape), dtype=loss.dtype, device=loss.device)
+            idx = torch.arange(nm, device=loss.device)
+            sel[idx, idx] = go
+            try:
+                grads = torch.autograd.grad(loss, var_list, grad_outputs=sel, retain_graph=True, allow_unused=True,
+                                            is_grads_batched=True)
+            except RuntimeError as e:
+                raise RuntimeError(f'microbatch_gradients="batched": the backward failed under is_grads_batched '
+                                   f'(an op without a batching rule does); microbatch_gradients="loop" takes '
+                                   f'one backward per microbatch instead ({e})') from e
+            return [g.detach() if g is not None else torch.zeros((nm,) + tuple(v.shape), dtype=v.dtype, device=v.device)
+                    for g, v in zip(grads, var_list)]
 
         def apply_gradients(self, grads_and_vars):
             for g, v in grads_and_vars:

@@ -806,6 +806,40 @@ int efl_dp_noise(const float* x, float* out, int64_t n, int mode, float sigma, f
 int efl_dp_box_muller(const uint32_t* x0, const uint32_t* x1, int64_t n, int nb, float* r, float* sn,
                       float* cs, float* z0, float* z1, void* stream);
 
+/* The whole per-microbatch step of compute_gradients (:148-216) over stacked gradients, in two or
+ * three launches (csrc/dpclip.hip). A record has nvars variables; variable v's microbatch gradients
+ * are rows of `numel` floats, row r at grads + r * row_stride. For every variable
+ *   out[j] = noise(sum over r, in row order, of grads[r][j] * scale_r) / divisor,
+ * the sum in fp32 from 0.0f, every product and every addition rounded on its own (the float the
+ * reference's loop `s = s + g_r * scale_r` makes), the noise and the division exactly efl_dp_noise's
+ * (noise_mode, sigma, divisor as there; element j of a variable takes normal j % 4 of block
+ * ctr0 + j / 4 under `seed`).
+ * clip_mode 0: no scale (the sum of the rows; scales is not looked at).
+ * clip_mode 1: scale_r = (float)(clip * min(1 / sqrt(S_r), 1 / clip)), S_r the sum of squares of row r
+ *   over ALL variables, accumulated in double in a fixed order (no atomics: the same bytes on every
+ *   run), clip = l2_norm_clip > 0; S_r = 0 gives 1 and an infinite S_r gives 0. The scales are
+ *   written to `scales` (device, [rows]). `work` is device scratch of at least
+ *   efl_dp_clip_work_elems(numels, nvars, rows) doubles.
+ * clip_mode 2: scale_r = scales[r], given.
+ * `vars` is a HOST array; it travels to the kernels by value, 64 variables per launch, so the call
+ * allocates nothing, copies nothing and is stream-ordered. Rows are read with 16-byte loads when
+ * grads is 16-byte aligned and row_stride % 4 == 0, with dword loads otherwise. A variable with
+ * numel == 0 is skipped; nvars == 0 is a no-op. out must not overlap any grads.
+ * EFL_E_INVALID_ARGUMENT, before any HIP call, for: a mode out of range, a zero or NaN divisor,
+ * l2_norm_clip <= 0 in clip_mode 1, rows <= 0, nvars < 0, a null table, a null grads / out, an out
+ * that is not 16-byte aligned, row_stride < numel, a null scales in clip_mode 1 / 2, and a null or
+ * short work in clip_mode 1. */
+typedef struct efl_dp_var {
+  const float* grads;      /* device: row r at grads + r * row_stride, numel floats per row */
+  float* out;              /* device: [numel], 16-byte aligned */
+  int64_t numel, row_stride;   /* row_stride >= numel */
+  uint64_t ctr0;           /* first Philox block of this variable's noise */
+} efl_dp_var;
+int64_t efl_dp_clip_work_elems(const int64_t* numels, int64_t nvars, int64_t rows);
+int efl_dp_clip_sum(const efl_dp_var* vars, int64_t nvars, int64_t rows, int clip_mode, float l2_norm_clip,
+                    int noise_mode, float sigma, float divisor, uint64_t seed, float* scales, double* work,
+                    int64_t work_elems, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

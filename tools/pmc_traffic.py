@@ -55,6 +55,7 @@ def main():
                                  "algorithmic_bytes": 20 * n}
     with open(os.path.join(root, "profiles", "pmc_traffic.json"), "w") as f:
         json.dump(out, f, indent=1)
+        f.write("\n")
     print(json.dumps(out, indent=1))
 
 
