@@ -13,7 +13,7 @@
 //   k_dp_sqnorm    grid (row, variable, 8,192-element tile of the row): the tile's sum of squares
 //                  in double, wave shuffles then LDS, one partial per workgroup into its own slot
 //                  of `work`; no atomics, so the same bytes on every run;
-//   k_dp_scales    one wave per row: the row's slots summed in a fixed order, still in double, and
+//   k_dp_scales    (dp_scales.h) one wave per row: the row's slots summed in a fixed order, still in double, and
 //                  scale_i = float(clip * min(1 / sqrt(S_i), 1 / clip)) rounded once;
 //   k_dp_clip_sum  one lane owns one 4-column group of one variable (one Philox block, as
 //                  k_dp_noise): it walks the rows IN ORDER, acc = acc + g * scale_i in fp32 with no
@@ -32,6 +32,7 @@
 
 #include "common.h"
 #include "dp_normal.h"
+#include "dp_scales.h"
 
 // acc + g * scale rounds twice, as the reference's separate multiply and add do
 #pragma clang fp contract(off)
@@ -61,12 +62,6 @@ __device__ __forceinline__ int find_var(const dp_chunk& c, uint32_t tile) {
     else hi = mid;
   }
   return lo;
-}
-
-__device__ __forceinline__ double wave_sum(double s) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
-  return s;
 }
 
 // Pass 1. Workgroup (row, tile): sum of squares of up to kNormTile elements of one variable's row.
@@ -118,21 +113,6 @@ __global__ __launch_bounds__(kBlock) void k_dp_sqnorm(const dp_chunk c, uint32_t
 #pragma unroll
     for (int w = 1; w < kBlock / 64; ++w) s += part[w];
     work[(long long)row * slots + slot0 + tile] = s;
-  }
-}
-
-// One wave per row: S = the row's slots (lane l takes l, l + 64, ... in order, then the wave's tree),
-// scale = clip * min(1 / sqrt(S), 1 / clip) in double, rounded to float once. S = 0 gives 1, an
-// infinite S gives 0, a NaN stays a NaN (torch.minimum's rule, as GaussianSumQuery.preprocess_record).
-__global__ __launch_bounds__(64) void k_dp_scales(const double* __restrict__ work, long long slots, double clip,
-                                                  float* __restrict__ scales) {
-  const double* w = work + (long long)blockIdx.x * slots;
-  double s = 0.0;
-  for (long long i = threadIdx.x; i < slots; i += 64) s += w[i];
-  s = wave_sum(s);
-  if (threadIdx.x == 0) {
-    const double inv = 1.0 / sqrt(s), ic = 1.0 / clip;
-    scales[blockIdx.x] = (float)(clip * ((inv < ic || inv != inv) ? inv : ic));
   }
 }
 

@@ -55,6 +55,10 @@ _SIGS = {
     "efl_dp_clip_work_elems": ([_vp, _i64, _i64], _i64),
     "efl_dp_clip_sum": ([_vp, _i64, _i64, _i32, ctypes.c_float, _i32, ctypes.c_float, ctypes.c_float,
                          ctypes.c_uint64, _vp, _vp, _i64, _vp], _i32),
+    # the same step for dense layers from inputs and output gradients: layers is a host array of DpDense
+    "efl_dp_dense_work_elems": ([_i64, _i64], _i64),
+    "efl_dp_dense_clip_sum": ([_vp, _i64, _i64, _i64, _i32, ctypes.c_float, _i32, ctypes.c_float, ctypes.c_float,
+                               ctypes.c_uint64, _vp, _vp, _i64, _vp], _i32),
     # RSA blind-signature PSI (efl.psi; include/efl_hip.h efl_rsa_*): contexts and info structs as void*
     "efl_rsa_ctx_create": ([_vp], _i32),
     "efl_rsa_ctx_destroy": ([_vp], _i32),
@@ -117,6 +121,13 @@ class DpVar(ctypes.Structure):
     """efl_dp_var (include/efl_hip.h): one variable of efl_dp_clip_sum's record, its stacked
     microbatch gradients (row r at grads + r * row_stride) and its [numel] output."""
     _fields_ = [("grads", _vp), ("out", _vp), ("numel", _i64), ("row_stride", _i64), ("ctr0", ctypes.c_uint64)]
+
+
+class DpDense(ctypes.Structure):
+    """efl_dp_dense (include/efl_hip.h): one dense layer of efl_dp_dense_clip_sum, its input x [B, in],
+    the gradient d [B, out] of the summed loss by its output, and its [out, in] / [out] outputs."""
+    _fields_ = [("x", _vp), ("x_row_stride", _i64), ("d", _vp), ("d_row_stride", _i64), ("w_out", _vp),
+                ("b_out", _vp), ("in_", _i64), ("out", _i64), ("ctr0_w", ctypes.c_uint64), ("ctr0_b", ctypes.c_uint64)]
 
 
 # TensorFlow DataType numbers (types.proto), as used by the C ABI and the wire format.

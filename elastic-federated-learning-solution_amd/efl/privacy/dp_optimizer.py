@@ -16,7 +16,7 @@ The noise and the division run as ONE HIP kernel per variable (csrc/mask.hip efl
 sum once, write the averaged noised gradient once) with TF's normal construction (Philox4x32-10,
 Box-Muller) from a per-process `NoiseStream`. No CPU fallback: the kernel needs the GPU.
 
-The per-microbatch gradients come one of two ways (`microbatch_gradients=`, process default by
+The per-microbatch gradients come one of three ways (`microbatch_gradients=`, process default by
 `set_microbatch_gradients`). "loop", the default: one autograd.grad per microbatch, the clip a
 torch reduction and the sum a torch addition per variable, as the reference's loop. "batched": ONE
 autograd.grad with is_grads_batched=True gives every variable's gradients stacked as [rows, ...],
@@ -24,7 +24,15 @@ and for float32 device records the norms, the clip scales, the row-ordered sum, 
 division are two or three HIP launches whatever the model (csrc/dpclip.hip efl_dp_clip_sum,
 `dp_clip_sum_noise`): the same sum as the loop's given the same scales, the scales from a double
 accumulation instead of float32 reductions. Custom queries and other dtypes take
-`_SumQuery.accumulate_batch`, the loop restated over the stack.
+`_SumQuery.accumulate_batch`, the loop restated over the stack. "factored", for models whose
+variables are all weights and biases of torch.nn.Linear layers given as `dense_layers=`: forward hooks
+keep each layer's input X and output, ONE ordinary autograd.grad of the loss to the outputs gives D,
+and the norms (from the layers' r x r Gram matrices), the clipped sum (one fp32-MFMA GEMM D^T diag(s) X
+per layer), the noise and the division are csrc/dpdense.hip's efl_dp_dense_clip_sum
+(`dp_dense_clip_sum_noise`): no [rows, out, in] stack exists at any point. It needs microbatches of at
+most 16 examples, the stock queries, float32, and examples that are independent in the forward pass
+(no batch statistics), which cannot be checked; anything else raises InvalidArgumentError, as there is
+no stack to fall back on. A model that mixes dense and other variables is out of its scope.
 
 Torch mapping. TF optimisers get their variables at minimize time; torch ones at construction.
 These classes take either: `params` (as `params=`, or first positional with the DP arguments as
@@ -83,23 +91,27 @@ def dp_noise(x: torch.Tensor, mode: int, sigma: float, divisor: float = 1.0, str
     return lib.back(out, home)
 
 
-MICROBATCH_GRADIENTS = ("loop", "batched")
+MICROBATCH_GRADIENTS = ("loop", "batched")       # for any model and any query
+DENSE_MICROBATCH_GRADIENTS = ("factored",)        # for models of registered Linear layers (dense_layers=)
+MAX_ROWS_PER_MICROBATCH = 16                      # efl_dp_dense_clip_sum's limit on batch rows per microbatch
 _microbatch_gradients = "loop"
 
 
 @exporter.export("privacy.set_microbatch_gradients")
 def set_microbatch_gradients(name: str) -> None:
     """The process default of the DP optimisers' `microbatch_gradients` keyword: "loop" (one
-    autograd.grad and one torch clip-and-add per microbatch, the default) or "batched" (one batched
-    autograd.grad, then efl_dp_clip_sum over the stacked gradients)."""
+    autograd.grad and one torch clip-and-add per microbatch, the default), "batched" (one batched
+    autograd.grad, then efl_dp_clip_sum over the stacked gradients) or "factored" (one ordinary
+    autograd.grad to the registered dense layers' outputs, then efl_dp_dense_clip_sum)."""
     global _microbatch_gradients
     _microbatch_gradients = _resolve_microbatch_gradients(name)
 
 
 def _resolve_microbatch_gradients(name):
     name = _microbatch_gradients if name is None else name
-    if name not in MICROBATCH_GRADIENTS:
-        raise ValueError(f"microbatch_gradients must be one of {MICROBATCH_GRADIENTS}, got {name!r}")
+    if name not in MICROBATCH_GRADIENTS + DENSE_MICROBATCH_GRADIENTS:
+        raise ValueError(f"microbatch_gradients must be one of {MICROBATCH_GRADIENTS + DENSE_MICROBATCH_GRADIENTS}, "
+                         f"got {name!r}")
     return name
 
 
@@ -162,6 +174,101 @@ def dp_clip_sum_noise(stacked, l2_norm_clip, mode: int, sigma: float, divisor: f
                                         lib.stream_handle(dev)))
     if return_scales:
         return outs, torch.ones(rows, device=dev) if scales is None else scales
+    return outs
+
+
+def _rows_2d(t):
+    """A [B, width] float32 device tensor as efl_dp_dense_clip_sum reads it: rows contiguous and at
+    least `width` apart (a padded row stride is taken as it is), anything else made contiguous."""
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]) or t.data_ptr() % 4:
+        t = t.contiguous()
+    return t
+
+
+def _dense_clip_sum(layers, rows, l2_norm_clip, mode, sigma, divisor, seed, ctrs, scales):
+    """efl_dp_dense_clip_sum over checked layers [(x, d, has_bias)]; ctrs: per layer the first Philox
+    block of (weight, bias). Returns ([(w_grad, b_grad | None)], scales | None)."""
+    dev, B = layers[0][0].device, layers[0][0].shape[0]
+    like = []
+    for x, d, has_bias in layers:
+        like.append(torch.empty(d.shape[1], x.shape[1], device="meta"))
+        if has_bias:
+            like.append(torch.empty(d.shape[1], device="meta"))
+    flat = iter(lib._carve(like, torch.float32, dev))
+    arr, outs, keep = (lib.DpDense * len(layers))(), [], []
+    for rec, (x, d, has_bias), (cw, cb) in zip(arr, layers, ctrs):
+        x, d = _rows_2d(x), _rows_2d(d)
+        keep += [x, d]
+        w, b = next(flat), next(flat) if has_bias else None
+        rec.x, rec.x_row_stride, rec.d, rec.d_row_stride = x.data_ptr(), max(x.stride(0), x.shape[1]), d.data_ptr(), max(d.stride(0), d.shape[1])
+        rec.w_out, rec.b_out, rec.in_, rec.out = w.data_ptr(), None if b is None else b.data_ptr(), x.shape[1], d.shape[1]
+        rec.ctr0_w, rec.ctr0_b = cw, cb
+        outs.append((w, b))
+    clip_mode = 2 if scales is not None else 0 if l2_norm_clip is None else 1
+    work, work_elems = None, 0
+    if clip_mode == 2:
+        scales = lib.as_tensor(scales).detach().to(dev, torch.float32).contiguous()
+        if scales.shape != (rows,):
+            raise errors.InvalidArgumentError(f"dp_dense_clip_sum_noise: scales must be [{rows}]")
+    elif clip_mode == 1:
+        work_elems = lib.raw().efl_dp_dense_work_elems(len(layers), rows)
+        if work_elems < 0:
+            lib.check(int(work_elems))
+        work = torch.empty(max(work_elems, 1), dtype=torch.float64, device=dev)
+        scales = torch.empty(rows, dtype=torch.float32, device=dev)
+    lib.check(lib.raw().efl_dp_dense_clip_sum(arr, len(layers), B, rows, clip_mode, float(l2_norm_clip or 0.0),
+                                              int(mode), float(sigma), float(divisor), seed,
+                                              None if scales is None else scales.data_ptr(),
+                                              None if work is None else work.data_ptr(), work_elems,
+                                              lib.stream_handle(dev)))
+    return outs, scales
+
+
+def _check_dense_layers(layers, rows, who):
+    layers = [(lib.as_tensor(x).detach(), lib.as_tensor(d).detach(), bool(has_bias)) for x, d, has_bias in layers]
+    dev, B = layers[0][0].device, layers[0][0].shape[0] if layers[0][0].dim() else 0
+    for x, d, _ in layers:
+        if x.dtype != torch.float32 or d.dtype != torch.float32:
+            raise errors.InvalidArgumentError(f"{who}: x and d must be float32, got {x.dtype} and {d.dtype}")
+        if x.device != dev or d.device != dev or dev.type != "cuda":
+            raise errors.InvalidArgumentError(f"{who}: every x and d lies on one ROCm device")
+        if x.dim() != 2 or d.dim() != 2 or x.shape[0] != B or d.shape[0] != B or 0 in x.shape or 0 in d.shape:
+            raise errors.InvalidArgumentError(
+                f"{who}: a layer takes x [B, in] and d [B, out] with B = {B}, got {tuple(x.shape)} and {tuple(d.shape)}")
+    rows = int(rows)
+    if rows < 1 or B % rows:
+        raise errors.InvalidArgumentError(f"{who}: {rows} microbatches do not divide the batch of {B}")
+    if B // rows > MAX_ROWS_PER_MICROBATCH:
+        raise errors.InvalidArgumentError(f"{who}: {B // rows} examples per microbatch, at most "
+                                          f"{MAX_ROWS_PER_MICROBATCH} (r > {MAX_ROWS_PER_MICROBATCH})")
+    return layers, rows
+
+
+@exporter.export("privacy.dp_dense_clip_sum_noise")
+def dp_dense_clip_sum_noise(layers, rows: int, l2_norm_clip, mode: int, sigma: float, divisor: float = 1.0,
+                            stream: NoiseStream | None = None, scales=None, return_scales: bool = False):
+    """efl_dp_dense_clip_sum: a DP-SGD step's clipped, summed, noised and divided gradients of dense
+    layers from their inputs and output gradients, without the per-microbatch gradients. `layers` is
+    a list of (x [B, in], d [B, out], has_bias) float32 ROCm tensors, d the gradient of the SUM of the
+    per-example losses by the layer's output; microbatch i is the B / rows (at most 16) consecutive
+    rows from i * B / rows. Returns [(w_grad [out, in], b_grad [out] | None), ...]: per layer
+    noise(sum_i scale_i D_i^T X_i) / divisor and noise(sum_i scale_i colsum(D_i)) / divisor with
+    efl_dp_noise's `mode`, `sigma` and `divisor`; the noise positions are taken from `stream` (default:
+    the process's) one take(numel) per variable, weight then bias, in layer order.
+    scale_i: 1 with l2_norm_clip None and no `scales`; `scales` ([rows] float32) when given; else
+    clip * min(1 / ||g_i||, 1 / clip), g_i microbatch i's gradient of all the layers' variables, its
+    norm from the layers' Gram matrices in double. return_scales: also return the [rows] scales."""
+    layers = list(layers)
+    if not layers:
+        return ([], None) if return_scales else []
+    layers, rows = _check_dense_layers(layers, rows, "dp_dense_clip_sum_noise")
+    ctrs, seed = [], None
+    for x, d, has_bias in layers:
+        seed, cw = (stream or _stream).take(d.shape[1] * x.shape[1])
+        ctrs.append((cw, (stream or _stream).take(d.shape[1])[1] if has_bias else 0))
+    outs, scales = _dense_clip_sum(layers, rows, l2_norm_clip, mode, sigma, divisor, seed, ctrs, scales)
+    if return_scales:
+        return outs, torch.ones(rows, device=layers[0][0].device) if scales is None else scales
     return outs
 
 
@@ -310,9 +417,17 @@ def make_optimizer_class(cls):
         def __init__(self, *args, **kwargs):
             """(dp_sum_query, num_microbatches=None, unroll_microbatches=False, [params], **opt
             kwargs), or torch style (params, dp_sum_query=..., ...). microbatch_gradients= "loop" /
-            "batched" (keyword only; None: the process default, set_microbatch_gradients)."""
+            "batched" / "factored" (keyword only; None: the process default, set_microbatch_gradients).
+            dense_layers= (keyword only): the torch.nn.Linear modules "factored" takes its gradients
+            from; each gets a forward hook that keeps its input and output of the current step."""
             self._microbatch_gradients = kwargs.pop("microbatch_gradients", None)
             _resolve_microbatch_gradients(self._microbatch_gradients)
+            self._dense = {}                # Linear module -> [(detached input, output)] since the last step
+            for layer in kwargs.pop("dense_layers", None) or ():
+                if not isinstance(layer, torch.nn.Linear):
+                    raise errors.InvalidArgumentError(f"dense_layers takes torch.nn.Linear modules, got {type(layer).__name__}")
+                self._dense[layer] = []
+                layer.register_forward_hook(self._keep_dense)
             if "learning_rate" in kwargs:
                 kwargs["lr"] = kwargs.pop("learning_rate")
             lead = _as_params(args[0]) if args else None
@@ -363,7 +478,15 @@ def make_optimizer_class(cls):
             loss = loss.reshape(nm, -1)
             grad_loss = None if grad_loss is None else grad_loss.reshape(nm, -1)
             params = self._dp_sum_query.derive_sample_params(self._global_state)
-            if _resolve_microbatch_gradients(self._microbatch_gradients) == "batched":
+            path = _resolve_microbatch_gradients(self._microbatch_gradients)
+            if path == "factored":
+                try:
+                    return list(zip(self._factored_gradients(loss, var_list, grad_loss, reduce_func, params, nm,
+                                                             batch_size), var_list))
+                finally:                    # the kept inputs and outputs belong to this step alone
+                    for seen in self._dense.values():
+                        seen.clear()
+            if path == "batched":
                 stacked = self._stacked_gradients(loss, var_list, grad_loss, reduce_func)
                 final, self._global_state = self._dp_sum_query.get_noised_batch(params, stacked, self._global_state,
                                                                                 divisor=float(nm))
@@ -405,6 +528,69 @@ def make_optimizer_class(cls):
                                    f'one backward per microbatch instead ({e})') from e
             return [g.detach() if g is not None else torch.zeros((nm,) + tuple(v.shape), dtype=v.dtype, device=v.device)
                     for g, v in zip(grads, var_list)]
+
+        def _keep_dense(self, layer, inputs, output):
+            # a forward pass outside autograd (an evaluation under no_grad) is not part of a step
+            if (torch.is_grad_enabled() and output.requires_grad
+                    and _resolve_microbatch_gradients(self._microbatch_gradients) == "factored"):
+                self._dense[layer].append((inputs[0].detach(), output))
+
+        def _factored_gradients(self, loss, var_list, grad_loss, reduce_func, params, nm, batch):
+            """The step's gradients of the registered dense layers' variables from ONE ordinary
+            backward to the layers' outputs and efl_dp_dense_clip_sum (csrc/dpdense.hip). Precondition
+            that cannot be checked here: the examples are independent in the forward pass (no batch
+            statistics), so that row k of d(sum of the loss)/d(output) is example k's own."""
+            who = 'microbatch_gradients="factored"'
+            q = self._dp_sum_query
+            if type(q) not in (GaussianSumQuery, ElementWiseGaussianSumQuery):
+                raise errors.InvalidArgumentError(
+                    f"{who}: only the stock GaussianSumQuery and ElementWiseGaussianSumQuery are fused, got "
+                    f"{type(q).__name__} (a subclass's overrides need the per-microbatch gradients)")
+            if callable(reduce_func):
+                raise errors.InvalidArgumentError(f"{who}: a callable REDUCE needs the per-microbatch losses")
+            owner = {}
+            for layer in self._dense:
+                owner[layer.weight] = (layer, 0)
+                if layer.bias is not None:
+                    owner[layer.bias] = (layer, 1)
+            used = {}                           # layer -> [index of its weight in var_list, of its bias]
+            for i, v in enumerate(var_list):
+                if v not in owner:
+                    raise errors.InvalidArgumentError(
+                        f"{who}: variable {i} of var_list {tuple(v.shape)} is not the weight or bias of a layer "
+                        f"given as dense_layers=")
+                used.setdefault(owner[v][0], [None, None])[owner[v][1]] = i
+            layers = []
+            for layer, (wi, bi) in used.items():
+                if wi is None:
+                    raise errors.InvalidArgumentError(f"{who}: the bias of {layer} is in var_list without its weight")
+                seen = self._dense[layer]
+                if len(seen) != 1:
+                    raise errors.InvalidArgumentError(
+                        f"{who}: {layer} ran {len(seen)} times since the last step; each dense layer runs once")
+                x, out = seen[0]
+                if x.dim() != 2 or x.shape[0] != batch or x.dtype != torch.float32 or out.dtype != torch.float32:
+                    raise errors.InvalidArgumentError(
+                        f"{who}: {layer} takes a float32 [B, in] input with B = {batch} per-example losses, got "
+                        f"{x.dtype} {tuple(x.shape)}")
+                layers.append((layer, wi, bi, x, out))
+            go = torch.ones_like(loss) if grad_loss is None else grad_loss.reshape(loss.shape)
+            ds = torch.autograd.grad(loss, [l[4] for l in layers], grad_outputs=go, retain_graph=True, allow_unused=True)
+            recs = [(x, d if d is not None else torch.zeros_like(out), bi is not None)
+                    for (_, _, bi, x, out), d in zip(layers, ds)]
+            recs, nm = _check_dense_layers(recs, nm, who)
+            takes = [_stream.take(v.numel()) for v in var_list]          # as the loop: var_list order
+            ctrs = [(takes[wi][1], takes[bi][1] if bi is not None else 0) for _, wi, bi, _, _ in layers]
+            if type(q) is GaussianSumQuery:
+                outs, _ = _dense_clip_sum(recs, nm, params, 1, q._stddev, float(nm), takes[0][0], ctrs, None)
+            else:
+                outs, _ = _dense_clip_sum(recs, nm, None, 0, q._noise_multiplier, float(nm), takes[0][0], ctrs, None)
+            final = [None] * len(var_list)
+            for (_, wi, bi, _, _), (w, b) in zip(layers, outs):
+                final[wi] = w
+                if bi is not None:
+                    final[bi] = b
+            return final
 
         def apply_gradients(self, grads_and_vars):
             for g, v in grads_and_vars:

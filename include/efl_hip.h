@@ -840,6 +840,38 @@ int efl_dp_clip_sum(const efl_dp_var* vars, int64_t nvars, int64_t rows, int cli
                     int noise_mode, float sigma, float divisor, uint64_t seed, float* scales, double* work,
                     int64_t work_elems, void* stream);
 
+/* The same step for dense (Linear) layers WITHOUT the stacked gradients (csrc/dpdense.hip). A layer
+ * gives its input x [B, in] and d [B, out], the gradient of the summed loss with respect to its
+ * output; microbatch i is the r = B / rows consecutive batch rows [i r, (i + 1) r), 1 <= r <= 16. Its
+ * weight gradient is G_i = D_i^T X_i and its bias gradient the column sums of D_i, so
+ *   S_i = sum over layers of sum_{a, b in i} (x_a . x_b)(d_a . d_b) [+ ||sum_a d_a||^2 with a bias]
+ * in double, in a fixed order, and for every layer
+ *   w_out [out, in] = noise(D^T diag(s_{k / r}) X) / divisor,   b_out [out] = noise(sum_k s_{k / r} d_k) / divisor,
+ * one fp32 GEMM with K = B on the matrix cores (s d rounded once, then fp32 accumulation in a fixed
+ * order: the same bytes on every run), with efl_dp_noise's noise and division. clip_mode, l2_norm_clip,
+ * mode, sigma, divisor, seed, scales ([rows]) and the clip_mode 1 formula are efl_dp_clip_sum's; element
+ * j of w_out takes normal j % 4 of block ctr0_w + j / 4, element j of b_out of block ctr0_b + j / 4.
+ * `work` is device scratch of efl_dp_dense_work_elems(nlayers, rows) doubles (clip_mode 1 only).
+ * `layers` is a HOST array; it travels to the kernels by value, 32 layers per launch: no allocation,
+ * no copy, stream-ordered. b_out NULL: the layer has no bias (nothing of it enters S_i). The outputs
+ * must not overlap the inputs. nlayers == 0 is a no-op.
+ * EFL_E_INVALID_ARGUMENT, before any HIP call, for: a mode out of range, a zero or NaN divisor,
+ * l2_norm_clip <= 0 in clip_mode 1, rows <= 0, B <= 0, B % rows != 0, B / rows > 16, a null table, a null
+ * x / d / w_out, in or out < 1, a row stride below its width, a w_out that is not 16-byte aligned,
+ * a null scales in clip_mode 1 / 2, and a null or short work in clip_mode 1. */
+typedef struct efl_dp_dense {
+  const float* x;  int64_t x_row_stride;   /* [B, in]  layer input          */
+  const float* d;  int64_t d_row_stride;   /* [B, out] dLoss/d(output)      */
+  float* w_out;                            /* [out, in] contiguous          */
+  float* b_out;                            /* [out] or NULL (no bias)       */
+  int64_t in, out;
+  uint64_t ctr0_w, ctr0_b;                 /* first Philox block of each    */
+} efl_dp_dense;
+int64_t efl_dp_dense_work_elems(int64_t nlayers, int64_t rows);
+int efl_dp_dense_clip_sum(const efl_dp_dense* layers, int64_t nlayers, int64_t B, int64_t rows,
+                          int clip_mode, float l2_norm_clip, int mode, float sigma, float divisor,
+                          uint64_t seed, float* scales, double* work, int64_t work_elems, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

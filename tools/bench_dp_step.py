@@ -7,6 +7,9 @@
            forward pass is outside the timed window (both paths share it); the window is a host clock
            around compute_gradients that ends in a device synchronise, `--rounds` interleaved rounds
            after a warm-up, the median reported. The two results are compared first.
+           --model criteo_mlp (the criteo leader's dense stack, 181 -> 64 -> 16 -> 2) or wide_mlp
+           (1024 -> 1024 -> 1024 -> 10) times microbatch_gradients="factored" (csrc/dpdense.hip)
+           beside the two, with each path's peak device memory over a step.
   kernels  efl_dp_clip_sum alone at [256, 1 Mi] float32 (clip mode 1: the norm pass reads the stack
            once, the sum pass once more; clip mode 0: one read), HIP events around `--inner` calls,
            as a fraction of the 8 TB/s HBM peak: algorithmic bytes (reads of the stack + one write of
@@ -31,6 +34,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--inner", type=int, default=20)
 ap.add_argument("--batch", type=int, default=256)
+ap.add_argument("--model", choices=["dp_cnn", "criteo_mlp", "wide_mlp"], default="dp_cnn")
+ap.add_argument("--no-kernels", action="store_true", help="skip the efl_dp_clip_sum kernel measurement")
 ap.add_argument("--kernel-shape", type=int, nargs=2, default=[256, 1 << 20])
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
@@ -55,19 +60,30 @@ nn = torch.nn
 model = nn.Sequential(nn.Conv2d(1, 16, 8, stride=2, padding=3), nn.ReLU(), nn.MaxPool2d(2, 1),
                       nn.Conv2d(16, 32, 4, stride=2), nn.ReLU(), nn.MaxPool2d(2, 1), nn.Flatten(),
                       nn.Linear(512, 32), nn.ReLU(), nn.Linear(32, 10)).to(dev)
-params = list(model.parameters())
 x = torch.randn(args.batch, 1, 28, 28, device=dev)
-y = torch.randint(0, 10, (args.batch,), device=dev)
-opts = {p: efl.privacy.DPGradientDescentGaussianOptimizer(params, noise_multiplier=1.0, l2_norm_clip=1.0,
-                                                          learning_rate=0.25, microbatch_gradients=p)
-        for p in ("loop", "batched")}
+paths = ("loop", "batched")
+if args.model != "dp_cnn":
+    widths = (181, 64, 16, 2) if args.model == "criteo_mlp" else (1024, 1024, 1024, 10)
+    model = nn.Sequential(*[m for i, o in zip(widths, widths[1:]) for m in (nn.Linear(i, o), nn.ReLU())][:-1]).to(dev)
+    x = torch.randn(args.batch, widths[0], device=dev)
+    paths += ("factored",)
+# "factored" counts the forward passes of its layers between steps: it gets a copy of the model
+import copy  # noqa: E402
+models = {p: copy.deepcopy(model) if p == "factored" else model for p in paths}
+params = list(model.parameters())
+y = torch.randint(0, model[-1].out_features, (args.batch,), device=dev)
+opts = {p: efl.privacy.DPGradientDescentGaussianOptimizer(list(models[p].parameters()), noise_multiplier=1.0,
+                                                          l2_norm_clip=1.0, learning_rate=0.25, microbatch_gradients=p,
+                                                          dense_layers=[m for m in models[p] if isinstance(m, nn.Linear)]
+                                                          if p == "factored" else None)
+        for p in paths}
 
 
 def step(path):
-    loss = nn.functional.cross_entropy(model(x), y, reduction="none")
+    loss = nn.functional.cross_entropy(models[path](x), y, reduction="none")
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    gv = opts[path].compute_gradients(loss, params)
+    gv = opts[path].compute_gradients(loss, list(models[path].parameters()))
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) * 1e3, [g for g, _ in gv]
 
@@ -77,20 +93,30 @@ for p in opts:
     efl.privacy.set_noise_seed(5, 0)
     grads[p] = step(p)[1]
 # same noise positions; the sums differ by the scales' rounding (fp32 reductions against double)
-diff = max(float((a - b).abs().max() / (b.abs().max() + 1e-30)) for a, b in zip(grads["batched"], grads["loop"]))
+diff = max(float((a - b).abs().max() / (b.abs().max() + 1e-30)) for p in paths[1:]
+           for a, b in zip(grads[p], grads["loop"]))
 assert diff < 1e-4, diff
+del grads
+peak = {}
 for p in opts:
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
     step(p)
+    peak[p] = torch.cuda.max_memory_allocated()
 times = {p: [] for p in opts}
 for _ in range(args.rounds):
     for p in opts:
         times[p].append(step(p)[0])
 med = {p: float(np.median(t)) for p, t in times.items()}
-emit({"bench": "dp_step_compute_gradients", "model": "dp_cnn", "batch": args.batch, "microbatches": args.batch,
+emit({"bench": "dp_step_compute_gradients", "model": args.model, "batch": args.batch, "microbatches": args.batch,
       "variables": len(params), "floats": sum(p.numel() for p in params), "rounds": args.rounds,
       "ms_per_step": {p: round(v, 3) for p, v in med.items()},
       "ms_min_max": {p: [round(min(t), 3), round(max(t), 3)] for p, t in times.items()},
-      "loop_over_batched": round(med["loop"] / med["batched"], 2), "max_rel_diff": diff})
+      "peak_bytes": peak, "loop_over_batched": round(med["loop"] / med["batched"], 2),
+      **({"batched_over_factored": round(med["batched"] / med["factored"], 2)} if "factored" in med else {}),
+      "max_rel_diff": diff})
+if args.no_kernels:
+    sys.exit(0)
 
 # ---- the kernels alone -------------------------------------------------------------------------
 R, N = args.kernel_shape
