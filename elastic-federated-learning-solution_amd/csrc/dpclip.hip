@@ -307,3 +307,12 @@ EFL_API int efl_dp_clip_sum(const efl_dp_var* vars, int64_t nvars, int64_t rows,
   });
   return hip_status(hipGetLastError(), "efl_dp_clip_sum");
 }
+
+EFL_API int efl_dp_scales(const double* work, int64_t slots, int64_t rows, float l2_norm_clip, float* scales,
+                          void* stream) {
+  if (!(l2_norm_clip > 0.0f)) { set_error("efl_dp_scales: l2_norm_clip must be positive"); return EFL_E_INVALID_ARGUMENT; }
+  if (rows <= 0 || rows > 0x7fffffffll || slots < 0) { set_error("efl_dp_scales: 0 < rows < 2^31 and slots >= 0"); return EFL_E_INVALID_ARGUMENT; }
+  if (!work || !aligned(work, 8) || !scales || !aligned(scales, 4)) { set_error("efl_dp_scales: null or misaligned buffer"); return EFL_E_INVALID_ARGUMENT; }
+  k_dp_scales<<<(unsigned)rows, 64, 0, (hipStream_t)stream>>>(work, slots, (double)l2_norm_clip, scales);
+  return hip_status(hipGetLastError(), "efl_dp_scales");
+}

@@ -361,6 +361,31 @@ EFL_API int64_t efl_dp_dense_work_elems(int64_t nlayers, int64_t rows) {
   return nlayers * rows;
 }
 
+EFL_API int efl_dp_dense_sqnorm(const efl_dp_dense* layers, int64_t nlayers, int64_t B, int64_t rows, double* work,
+                                int64_t slot0, int64_t slots, void* stream) {
+  constexpr int64_t kMax = 0x7fffffff;
+  if (nlayers < 0 || rows <= 0 || B <= 0 || B > kMax) { set_error("efl_dp_dense_sqnorm: nlayers must be >= 0, rows > 0 and 0 < B < 2^31"); return EFL_E_INVALID_ARGUMENT; }
+  if (B % rows != 0 || B / rows > kMaxR) { set_error("efl_dp_dense_sqnorm: rows (%lld) must divide B (%lld) into at most %d batch rows each", (long long)rows, (long long)B, kMaxR); return EFL_E_INVALID_ARGUMENT; }
+  if (nlayers == 0) return EFL_OK;
+  if (!layers) { set_error("efl_dp_dense_sqnorm: null layer table"); return EFL_E_INVALID_ARGUMENT; }
+  for (int64_t i = 0; i < nlayers; ++i) {
+    const efl_dp_dense& L = layers[i];
+    if (L.in <= 0 || L.out <= 0 || L.in > kMax || L.out > kMax || !L.x || !L.d || !aligned(L.x, 4) || !aligned(L.d, 4) ||
+        L.x_row_stride < L.in || L.d_row_stride < L.out) {
+      set_error("efl_dp_dense_sqnorm: layer %lld: null or misaligned x / d, in or out < 1, or a row stride below its width", (long long)i);
+      return EFL_E_INVALID_ARGUMENT;
+    }
+  }
+  if (!work || !aligned(work, 8) || slot0 < 0 || slots > INT64_MAX / 16 / rows || slot0 > slots - nlayers) {
+    set_error("efl_dp_dense_sqnorm: work must hold rows x slots doubles with the layers' %lld slots in [slot0, slots)", (long long)nlayers);
+    return EFL_E_INVALID_ARGUMENT;
+  }
+  for_chunks(layers, nlayers, [&](const dd_chunk& c, int64_t i0) {
+    k_dp_dense_sqnorm<<<dim3((unsigned)rows, (unsigned)c.n), kBlock, 0, (hipStream_t)stream>>>(c, (int)(B / rows), slot0 + i0, slots, work);
+  });
+  return hip_status(hipGetLastError(), "efl_dp_dense_sqnorm");
+}
+
 EFL_API int efl_dp_dense_clip_sum(const efl_dp_dense* layers, int64_t nlayers, int64_t B, int64_t rows, int clip_mode,
                                   float l2_norm_clip, int mode, float sigma, float divisor, uint64_t seed,
                                   float* scales, double* work, int64_t work_elems, void* stream) {

@@ -59,6 +59,16 @@ _SIGS = {
     "efl_dp_dense_work_elems": ([_i64, _i64], _i64),
     "efl_dp_dense_clip_sum": ([_vp, _i64, _i64, _i64, _i32, ctypes.c_float, _i32, ctypes.c_float, ctypes.c_float,
                                ctypes.c_uint64, _vp, _vp, _i64, _vp], _i32),
+    # the pieces of a step over a model of dense and conv layers: both families' norm slots in one work
+    # buffer, one scales launch, then each family's sum with given scales
+    "efl_dp_dense_sqnorm": ([_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp], _i32),
+    "efl_dp_scales": ([_vp, _i64, _i64, ctypes.c_float, _vp, _vp], _i32),
+    # the same step for Conv2d layers from inputs and output gradients: layers is a host array of DpConv
+    "efl_dp_conv_work_elems": ([_vp, _i64, _i64], _i64),
+    "efl_dp_conv_partial_elems": ([_vp, _i64, _i64, _i64], _i64),
+    "efl_dp_conv_sqnorm": ([_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp], _i32),
+    "efl_dp_conv_clip_sum": ([_vp, _i64, _i64, _i64, _i32, ctypes.c_float, _i32, ctypes.c_float, ctypes.c_float,
+                              ctypes.c_uint64, _vp, _vp, _i64, _vp, _i64, _vp], _i32),
     # RSA blind-signature PSI (efl.psi; include/efl_hip.h efl_rsa_*): contexts and info structs as void*
     "efl_rsa_ctx_create": ([_vp], _i32),
     "efl_rsa_ctx_destroy": ([_vp], _i32),
@@ -128,6 +138,16 @@ class DpDense(ctypes.Structure):
     the gradient d [B, out] of the summed loss by its output, and its [out, in] / [out] outputs."""
     _fields_ = [("x", _vp), ("x_row_stride", _i64), ("d", _vp), ("d_row_stride", _i64), ("w_out", _vp),
                 ("b_out", _vp), ("in_", _i64), ("out", _i64), ("ctr0_w", ctypes.c_uint64), ("ctr0_b", ctypes.c_uint64)]
+
+
+class DpConv(ctypes.Structure):
+    """efl_dp_conv (include/efl_hip.h): one Conv2d layer of efl_dp_conv_clip_sum, its input x
+    [B, cin, h, w], the gradient d [B, cout, ho, wo] of the summed loss by its output, its
+    [cout, cin, kh, kw] / [cout] outputs and its geometry."""
+    _fields_ = ([("x", _vp), ("d", _vp), ("w_out", _vp), ("b_out", _vp)] +
+                [(n, ctypes.c_int32) for n in ("cin", "h", "w", "cout", "ho", "wo", "kh", "kw", "sh", "sw", "ph", "pw",
+                                               "dh", "dw")] +
+                [("ctr0_w", ctypes.c_uint64), ("ctr0_b", ctypes.c_uint64)])
 
 
 # TensorFlow DataType numbers (types.proto), as used by the C ABI and the wire format.

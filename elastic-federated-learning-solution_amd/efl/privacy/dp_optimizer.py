@@ -32,7 +32,12 @@ per layer), the noise and the division are csrc/dpdense.hip's efl_dp_dense_clip_
 (`dp_dense_clip_sum_noise`): no [rows, out, in] stack exists at any point. It needs microbatches of at
 most 16 examples, the stock queries, float32, and examples that are independent in the forward pass
 (no batch statistics), which cannot be checked; anything else raises InvalidArgumentError, as there is
-no stack to fall back on. A model that mixes dense and other variables is out of its scope.
+no stack to fall back on. torch.nn.Conv2d layers (groups = 1, zero padding) given as `conv_layers=` take
+the same path through csrc/dpconv.hip's efl_dp_conv_clip_sum (`dp_conv_clip_sum_noise`): the norm pass
+forms each microbatch's [Cout, Cin kh kw] gradient on chip in double and drops it, the sum is one implicit
+GEMM over all (example, output position) pairs. A model of both kinds clips under ONE norm: both families
+write their partial sums of squares into one buffer, one launch makes the scales, and both sums take them
+(`dp_factored_clip_sum_noise`). A model with any other variable is out of its scope.
 
 Torch mapping. TF optimisers get their variables at minimize time; torch ones at construction.
 These classes take either: `params` (as `params=`, or first positional with the DP arguments as
@@ -185,10 +190,10 @@ def _rows_2d(t):
     return t
 
 
-def _dense_clip_sum(layers, rows, l2_norm_clip, mode, sigma, divisor, seed, ctrs, scales):
-    """efl_dp_dense_clip_sum over checked layers [(x, d, has_bias)]; ctrs: per layer the first Philox
-    block of (weight, bias). Returns ([(w_grad, b_grad | None)], scales | None)."""
-    dev, B = layers[0][0].device, layers[0][0].shape[0]
+def _dense_table(layers, ctrs):
+    """The DpDense table of checked dense layers with freshly carved outputs: (table, [(w_grad, b_grad |
+    None)], tensors to keep alive)."""
+    dev = layers[0][0].device
     like = []
     for x, d, has_bias in layers:
         like.append(torch.empty(d.shape[1], x.shape[1], device="meta"))
@@ -204,6 +209,15 @@ def _dense_clip_sum(layers, rows, l2_norm_clip, mode, sigma, divisor, seed, ctrs
         rec.w_out, rec.b_out, rec.in_, rec.out = w.data_ptr(), None if b is None else b.data_ptr(), x.shape[1], d.shape[1]
         rec.ctr0_w, rec.ctr0_b = cw, cb
         outs.append((w, b))
+    return arr, outs, keep
+
+
+def _dense_clip_sum(layers, rows, l2_norm_clip, mode, sigma, divisor, seed, ctrs, scales, table=None):
+    """efl_dp_dense_clip_sum over checked layers [(x, d, has_bias)]; ctrs: per layer the first Philox
+    block of (weight, bias); table: their _dense_table when the caller has made it. Returns
+    ([(w_grad, b_grad | None)], scales | None)."""
+    dev, B = layers[0][0].device, layers[0][0].shape[0]
+    arr, outs, keep = table or _dense_table(layers, ctrs)
     clip_mode = 2 if scales is not None else 0 if l2_norm_clip is None else 1
     work, work_elems = None, 0
     if clip_mode == 2:
@@ -270,6 +284,201 @@ def dp_dense_clip_sum_noise(layers, rows: int, l2_norm_clip, mode: int, sigma: f
     if return_scales:
         return outs, torch.ones(rows, device=layers[0][0].device) if scales is None else scales
     return outs
+
+
+def _pair(v, name):
+    """An int or a pair of ints as Conv2d takes them, as (vertical, horizontal)."""
+    try:
+        v = (int(v), int(v)) if isinstance(v, int) else tuple(int(a) for a in v)
+    except (TypeError, ValueError):
+        v = ()
+    if len(v) != 2:
+        raise errors.InvalidArgumentError(f"{name} must be an int or a pair of ints")
+    return v
+
+
+def _conv_padding(padding, kernel, dilation, who):
+    """Conv2d's padding as a pair of ints: "valid" is 0, "same" d (k - 1) / 2 (which has to be whole:
+    torch pads the odd one on one side only, which no symmetric padding reproduces)."""
+    if padding == "valid":
+        return 0, 0
+    if padding == "same":
+        total = [d * (k - 1) for k, d in zip(kernel, dilation)]
+        if any(t % 2 for t in total):
+            raise errors.InvalidArgumentError(
+                f'{who}: padding="same" with kernel {kernel} and dilation {dilation} pads d (k - 1) = {tuple(total)}, '
+                f"odd in a dimension, unevenly")
+        return total[0] // 2, total[1] // 2
+    return _pair(padding, "padding")
+
+
+def _check_conv_layers(layers, rows, who):
+    """[(x, d, has_bias, kernel, stride, padding, dilation)] with detached tensors and pairs of ints."""
+    out = []
+    for x, d, has_bias, kernel, stride, padding, dilation in layers:
+        x, d = lib.as_tensor(x).detach(), lib.as_tensor(d).detach()
+        kernel, stride, dilation = _pair(kernel, "kernel_size"), _pair(stride, "stride"), _pair(dilation, "dilation")
+        out.append((x, d, bool(has_bias), kernel, stride, _conv_padding(padding, kernel, dilation, who), dilation))
+    dev, B = out[0][0].device, out[0][0].shape[0] if out[0][0].dim() else 0
+    for x, d, *_ in out:
+        if x.dtype != torch.float32 or d.dtype != torch.float32:
+            raise errors.InvalidArgumentError(f"{who}: x and d must be float32, got {x.dtype} and {d.dtype}")
+        if x.device != dev or d.device != dev or dev.type != "cuda":
+            raise errors.InvalidArgumentError(f"{who}: every x and d lies on one ROCm device")
+        if x.dim() != 4 or d.dim() != 4 or x.shape[0] != B or d.shape[0] != B or 0 in x.shape or 0 in d.shape:
+            raise errors.InvalidArgumentError(
+                f"{who}: a conv layer takes x [B, Cin, H, W] and d [B, Cout, Ho, Wo] with B = {B}, got "
+                f"{tuple(x.shape)} and {tuple(d.shape)}")
+    rows = int(rows)
+    if rows < 1 or B % rows:
+        raise errors.InvalidArgumentError(f"{who}: {rows} microbatches do not divide the batch of {B}")
+    if B // rows > MAX_ROWS_PER_MICROBATCH:
+        raise errors.InvalidArgumentError(f"{who}: {B // rows} examples per microbatch, at most "
+                                          f"{MAX_ROWS_PER_MICROBATCH} (r > {MAX_ROWS_PER_MICROBATCH})")
+    return out, rows
+
+
+def _conv_table(layers, ctrs):
+    """The DpConv table of checked conv layers with freshly carved outputs: (table, [(w_grad, b_grad |
+    None)], tensors to keep alive)."""
+    dev, like = layers[0][0].device, []
+    for x, d, has_bias, kernel, *_ in layers:
+        like.append(torch.empty(d.shape[1], x.shape[1], *kernel, device="meta"))
+        if has_bias:
+            like.append(torch.empty(d.shape[1], device="meta"))
+    flat = iter(lib._carve(like, torch.float32, dev))
+    arr, outs, keep = (lib.DpConv * len(layers))(), [], []
+    for rec, (x, d, has_bias, kernel, stride, padding, dilation), (cw, cb) in zip(arr, layers, ctrs):
+        x, d = x.contiguous(), d.contiguous()
+        keep += [x, d]
+        w, b = next(flat), next(flat) if has_bias else None
+        rec.x, rec.d, rec.w_out, rec.b_out = x.data_ptr(), d.data_ptr(), w.data_ptr(), None if b is None else b.data_ptr()
+        _, rec.cin, rec.h, rec.w = x.shape
+        _, rec.cout, rec.ho, rec.wo = d.shape
+        (rec.kh, rec.kw), (rec.sh, rec.sw), (rec.ph, rec.pw), (rec.dh, rec.dw) = kernel, stride, padding, dilation
+        rec.ctr0_w, rec.ctr0_b = cw, cb
+        outs.append((w, b))
+    return arr, outs, keep
+
+
+def _elems(n):
+    if n < 0:
+        lib.check(int(n))
+    return int(n)
+
+
+def _conv_clip_sum(layers, rows, l2_norm_clip, mode, sigma, divisor, seed, ctrs, scales, table=None):
+    """efl_dp_conv_clip_sum over checked layers; ctrs: per layer the first Philox block of (weight,
+    bias); table: their _conv_table when the caller has made it. Returns ([(w_grad, b_grad | None)],
+    scales | None)."""
+    dev, B, raw = layers[0][0].device, layers[0][0].shape[0], lib.raw()
+    arr, outs, keep = table or _conv_table(layers, ctrs)
+    clip_mode = 2 if scales is not None else 0 if l2_norm_clip is None else 1
+    work, work_elems = None, 0
+    if clip_mode == 2:
+        scales = lib.as_tensor(scales).detach().to(dev, torch.float32).contiguous()
+        if scales.shape != (rows,):
+            raise errors.InvalidArgumentError(f"dp_conv_clip_sum_noise: scales must be [{rows}]")
+    elif clip_mode == 1:
+        work_elems = _elems(raw.efl_dp_conv_work_elems(arr, len(layers), rows))
+        work = torch.empty(max(work_elems, 1), dtype=torch.float64, device=dev)
+        scales = torch.empty(rows, dtype=torch.float32, device=dev)
+    pe = _elems(raw.efl_dp_conv_partial_elems(arr, len(layers), B, rows))
+    partials = torch.empty(max(pe, 4), dtype=torch.float32, device=dev)
+    lib.check(raw.efl_dp_conv_clip_sum(arr, len(layers), B, rows, clip_mode, float(l2_norm_clip or 0.0), int(mode),
+                                       float(sigma), float(divisor), seed,
+                                       None if scales is None else scales.data_ptr(),
+                                       None if work is None else work.data_ptr(), work_elems, partials.data_ptr(), pe,
+                                       lib.stream_handle(dev)))
+    return outs, scales
+
+
+def _take_layers(shapes, stream):
+    """One take(numel) per variable, weight then bias, in layer order: (seed, [(ctr0_w, ctr0_b)])."""
+    ctrs, seed = [], None
+    for wn, bn in shapes:
+        seed, cw = stream.take(wn)
+        ctrs.append((cw, stream.take(bn)[1] if bn else 0))
+    return seed, ctrs
+
+
+def _conv_numels(layers):
+    return [(d.shape[1] * x.shape[1] * k[0] * k[1], d.shape[1] if has_bias else 0) for x, d, has_bias, k, *_ in layers]
+
+
+@exporter.export("privacy.dp_conv_clip_sum_noise")
+def dp_conv_clip_sum_noise(layers, rows: int, l2_norm_clip, mode: int, sigma: float, divisor: float = 1.0,
+                           stream: NoiseStream | None = None, scales=None, return_scales: bool = False):
+    """efl_dp_conv_clip_sum: a DP-SGD step's clipped, summed, noised and divided gradients of Conv2d
+    layers (groups = 1, zero padding) from their inputs and output gradients, without the per-microbatch
+    gradients. `layers` is a list of (x [B, Cin, H, W], d [B, Cout, Ho, Wo], has_bias, kernel_size,
+    stride, padding, dilation): float32 ROCm tensors, d the gradient of the SUM of the per-example losses
+    by the layer's output, the rest as Conv2d takes them. Microbatch i is the B / rows (at most 16)
+    consecutive examples from i * B / rows. Returns [(w_grad [Cout, Cin, kh, kw], b_grad [Cout] | None)];
+    mode, sigma, divisor, scales, return_scales and the stream positions (one take(numel) per variable,
+    weight then bias, in layer order) are dp_dense_clip_sum_noise's. The norms come from the gradients
+    themselves, formed on chip in double and never stored."""
+    layers = list(layers)
+    if not layers:
+        return ([], None) if return_scales else []
+    layers, rows = _check_conv_layers(layers, rows, "dp_conv_clip_sum_noise")
+    seed, ctrs = _take_layers(_conv_numels(layers), stream or _stream)
+    outs, scales = _conv_clip_sum(layers, rows, l2_norm_clip, mode, sigma, divisor, seed, ctrs, scales)
+    if return_scales:
+        return outs, torch.ones(rows, device=layers[0][0].device) if scales is None else scales
+    return outs
+
+
+def _factored_clip_sum(dense, conv, rows, l2_norm_clip, mode, sigma, divisor, seed, dctrs, cctrs, scales):
+    """Checked dense and conv layers under ONE norm: (dense outs, conv outs, scales | None). With both
+    families and no given scales, both write their norm slots into one work buffer [rows, slots] (the
+    dense layers' first), efl_dp_scales makes the scales, and both sums run with them (clip_mode 2)."""
+    dtab = ctab = None
+    if dense and conv and scales is None and l2_norm_clip is not None:
+        dev, B, raw, h = dense[0][0].device, dense[0][0].shape[0], lib.raw(), lib.stream_handle(dense[0][0].device)
+        dtab, ctab = _dense_table(dense, dctrs), _conv_table(conv, cctrs)
+        slots = len(dense) + _elems(raw.efl_dp_conv_work_elems(ctab[0], len(conv), rows)) // rows
+        work = torch.empty(rows * slots, dtype=torch.float64, device=dev)
+        scales = torch.empty(rows, dtype=torch.float32, device=dev)
+        lib.check(raw.efl_dp_dense_sqnorm(dtab[0], len(dense), B, rows, work.data_ptr(), 0, slots, h))
+        lib.check(raw.efl_dp_conv_sqnorm(ctab[0], len(conv), B, rows, work.data_ptr(), len(dense), slots, h))
+        lib.check(raw.efl_dp_scales(work.data_ptr(), slots, rows, float(l2_norm_clip), scales.data_ptr(), h))
+    douts = couts = []
+    if dense:                               # one family alone takes its own norm pass (clip_mode 1)
+        douts, scales = _dense_clip_sum(dense, rows, l2_norm_clip, mode, sigma, divisor, seed, dctrs, scales, dtab)
+    if conv:
+        couts, scales = _conv_clip_sum(conv, rows, l2_norm_clip, mode, sigma, divisor, seed, cctrs, scales, ctab)
+    return douts, couts, scales
+
+
+@exporter.export("privacy.dp_factored_clip_sum_noise")
+def dp_factored_clip_sum_noise(dense_layers, conv_layers, rows: int, l2_norm_clip, mode: int, sigma: float,
+                               divisor: float = 1.0, stream: NoiseStream | None = None, scales=None,
+                               return_scales: bool = False):
+    """dp_dense_clip_sum_noise and dp_conv_clip_sum_noise over one model's layers under ONE shared clip
+    norm: scale_i = clip * min(1 / ||g_i||, 1 / clip) with g_i microbatch i's gradient of ALL the layers'
+    variables. `dense_layers` and `conv_layers` are those functions' lists (either may be empty); the
+    dense variables come first in the stream. Returns (dense_outs, conv_outs), and the scales after them
+    with return_scales."""
+    dense, conv = list(dense_layers), list(conv_layers)
+    who = "dp_factored_clip_sum_noise"
+    if not dense and not conv:
+        return ([], [], None) if return_scales else ([], [])
+    if dense:
+        dense, rows = _check_dense_layers(dense, rows, who)
+    if conv:
+        conv, rows = _check_conv_layers(conv, rows, who)
+    if dense and conv and (dense[0][0].shape[0] != conv[0][0].shape[0] or dense[0][0].device != conv[0][0].device):
+        raise errors.InvalidArgumentError(f"{who}: the dense and the conv layers take one batch on one device")
+    st = stream or _stream
+    seed, dctrs = _take_layers([(d.shape[1] * x.shape[1], d.shape[1] if b else 0) for x, d, b in dense], st)
+    seed_c, cctrs = _take_layers(_conv_numels(conv), st)
+    douts, couts, scales = _factored_clip_sum(dense, conv, rows, l2_norm_clip, mode, sigma, divisor,
+                                              seed if seed is not None else seed_c, dctrs, cctrs, scales)
+    if return_scales:
+        dev = (dense or conv)[0][0].device
+        return douts, couts, torch.ones(rows, device=dev) if scales is None else scales
+    return douts, couts
 
 
 def _fusable(query, cls, stacked):
@@ -418,8 +627,9 @@ def make_optimizer_class(cls):
             """(dp_sum_query, num_microbatches=None, unroll_microbatches=False, [params], **opt
             kwargs), or torch style (params, dp_sum_query=..., ...). microbatch_gradients= "loop" /
             "batched" / "factored" (keyword only; None: the process default, set_microbatch_gradients).
-            dense_layers= (keyword only): the torch.nn.Linear modules "factored" takes its gradients
-            from; each gets a forward hook that keeps its input and output of the current step."""
+            dense_layers= and conv_layers= (keyword only): the torch.nn.Linear and torch.nn.Conv2d
+            modules "factored" takes its gradients from; each gets a forward hook that keeps its input
+            and output of the current step."""
             self._microbatch_gradients = kwargs.pop("microbatch_gradients", None)
             _resolve_microbatch_gradients(self._microbatch_gradients)
             self._dense = {}                # Linear module -> [(detached input, output)] since the last step
@@ -427,6 +637,19 @@ def make_optimizer_class(cls):
                 if not isinstance(layer, torch.nn.Linear):
                     raise errors.InvalidArgumentError(f"dense_layers takes torch.nn.Linear modules, got {type(layer).__name__}")
                 self._dense[layer] = []
+                layer.register_forward_hook(self._keep_dense)
+            self._conv = {}                 # Conv2d module -> the same
+            for layer in kwargs.pop("conv_layers", None) or ():
+                if not isinstance(layer, torch.nn.Conv2d):
+                    raise errors.InvalidArgumentError(
+                        f"conv_layers takes torch.nn.Conv2d modules (no transposed, 1-d or 3-d convolutions), got "
+                        f"{type(layer).__name__}")
+                if layer.groups != 1 or layer.padding_mode != "zeros":
+                    raise errors.InvalidArgumentError(
+                        f"conv_layers takes convolutions with groups = 1 and padding_mode 'zeros', got groups = "
+                        f"{layer.groups} and padding_mode {layer.padding_mode!r}")
+                _conv_padding(layer.padding, layer.kernel_size, layer.dilation, "conv_layers")
+                self._conv[layer] = []
                 layer.register_forward_hook(self._keep_dense)
             if "learning_rate" in kwargs:
                 kwargs["lr"] = kwargs.pop("learning_rate")
@@ -484,7 +707,7 @@ def make_optimizer_class(cls):
                     return list(zip(self._factored_gradients(loss, var_list, grad_loss, reduce_func, params, nm,
                                                              batch_size), var_list))
                 finally:                    # the kept inputs and outputs belong to this step alone
-                    for seen in self._dense.values():
+                    for seen in (*self._dense.values(), *self._conv.values()):
                         seen.clear()
             if path == "batched":
                 stacked = self._stacked_gradients(loss, var_list, grad_loss, reduce_func)
@@ -533,13 +756,14 @@ def make_optimizer_class(cls):
             # a forward pass outside autograd (an evaluation under no_grad) is not part of a step
             if (torch.is_grad_enabled() and output.requires_grad
                     and _resolve_microbatch_gradients(self._microbatch_gradients) == "factored"):
-                self._dense[layer].append((inputs[0].detach(), output))
+                (self._dense if layer in self._dense else self._conv)[layer].append((inputs[0].detach(), output))
 
         def _factored_gradients(self, loss, var_list, grad_loss, reduce_func, params, nm, batch):
-            """The step's gradients of the registered dense layers' variables from ONE ordinary
-            backward to the layers' outputs and efl_dp_dense_clip_sum (csrc/dpdense.hip). Precondition
-            that cannot be checked here: the examples are independent in the forward pass (no batch
-            statistics), so that row k of d(sum of the loss)/d(output) is example k's own."""
+            """The step's gradients of the registered dense and conv layers' variables from ONE ordinary
+            backward to the layers' outputs, then efl_dp_dense_clip_sum (csrc/dpdense.hip) and
+            efl_dp_conv_clip_sum (csrc/dpconv.hip) under one shared norm. Precondition that cannot be
+            checked here: the examples are independent in the forward pass (no batch statistics), so
+            that row k of d(sum of the loss)/d(output) is example k's own."""
             who = 'microbatch_gradients="factored"'
             q = self._dp_sum_query
             if type(q) not in (GaussianSumQuery, ElementWiseGaussianSumQuery):
@@ -549,7 +773,7 @@ def make_optimizer_class(cls):
             if callable(reduce_func):
                 raise errors.InvalidArgumentError(f"{who}: a callable REDUCE needs the per-microbatch losses")
             owner = {}
-            for layer in self._dense:
+            for layer in (*self._dense, *self._conv):
                 owner[layer.weight] = (layer, 0)
                 if layer.bias is not None:
                     owner[layer.bias] = (layer, 1)
@@ -558,35 +782,46 @@ def make_optimizer_class(cls):
                 if v not in owner:
                     raise errors.InvalidArgumentError(
                         f"{who}: variable {i} of var_list {tuple(v.shape)} is not the weight or bias of a layer "
-                        f"given as dense_layers=")
+                        f"given as dense_layers= or conv_layers=")
                 used.setdefault(owner[v][0], [None, None])[owner[v][1]] = i
             layers = []
             for layer, (wi, bi) in used.items():
                 if wi is None:
                     raise errors.InvalidArgumentError(f"{who}: the bias of {layer} is in var_list without its weight")
-                seen = self._dense[layer]
+                is_conv = layer in self._conv
+                seen = (self._conv if is_conv else self._dense)[layer]
                 if len(seen) != 1:
                     raise errors.InvalidArgumentError(
-                        f"{who}: {layer} ran {len(seen)} times since the last step; each dense layer runs once")
+                        f"{who}: {layer} ran {len(seen)} times since the last step; each layer runs once")
                 x, out = seen[0]
-                if x.dim() != 2 or x.shape[0] != batch or x.dtype != torch.float32 or out.dtype != torch.float32:
+                if (x.dim() != (4 if is_conv else 2) or x.shape[0] != batch or x.dtype != torch.float32
+                        or out.dtype != torch.float32):
                     raise errors.InvalidArgumentError(
-                        f"{who}: {layer} takes a float32 [B, in] input with B = {batch} per-example losses, got "
-                        f"{x.dtype} {tuple(x.shape)}")
+                        f"{who}: {layer} takes a float32 {'[B, Cin, H, W]' if is_conv else '[B, in]'} input with "
+                        f"B = {batch} per-example losses, got {x.dtype} {tuple(x.shape)}")
                 layers.append((layer, wi, bi, x, out))
             go = torch.ones_like(loss) if grad_loss is None else grad_loss.reshape(loss.shape)
             ds = torch.autograd.grad(loss, [l[4] for l in layers], grad_outputs=go, retain_graph=True, allow_unused=True)
-            recs = [(x, d if d is not None else torch.zeros_like(out), bi is not None)
-                    for (_, _, bi, x, out), d in zip(layers, ds)]
-            recs, nm = _check_dense_layers(recs, nm, who)
+            dense, conv = [], []                # (position in `layers`, record)
+            for k, ((layer, _, bi, x, out), d) in enumerate(zip(layers, ds)):
+                d = d if d is not None else torch.zeros_like(out)
+                if layer in self._conv:
+                    conv.append((k, (x, d, bi is not None, layer.kernel_size, layer.stride, layer.padding, layer.dilation)))
+                else:
+                    dense.append((k, (x, d, bi is not None)))
+            drecs, crecs = [r for _, r in dense], [r for _, r in conv]
+            if drecs:
+                drecs, nm = _check_dense_layers(drecs, nm, who)
+            if crecs:
+                crecs, nm = _check_conv_layers(crecs, nm, who)
             takes = [_stream.take(v.numel()) for v in var_list]          # as the loop: var_list order
-            ctrs = [(takes[wi][1], takes[bi][1] if bi is not None else 0) for _, wi, bi, _, _ in layers]
-            if type(q) is GaussianSumQuery:
-                outs, _ = _dense_clip_sum(recs, nm, params, 1, q._stddev, float(nm), takes[0][0], ctrs, None)
-            else:
-                outs, _ = _dense_clip_sum(recs, nm, None, 0, q._noise_multiplier, float(nm), takes[0][0], ctrs, None)
+            ctr = [(takes[wi][1], takes[bi][1] if bi is not None else 0) for _, wi, bi, _, _ in layers]
+            clip, mode, sigma = (params, 1, q._stddev) if type(q) is GaussianSumQuery else (None, 0, q._noise_multiplier)
+            douts, couts, _ = _factored_clip_sum(drecs, crecs, nm, clip, mode, sigma, float(nm), takes[0][0],
+                                                 [ctr[k] for k, _ in dense], [ctr[k] for k, _ in conv], None)
             final = [None] * len(var_list)
-            for (_, wi, bi, _, _), (w, b) in zip(layers, outs):
+            for k, (w, b) in zip([k for k, _ in dense] + [k for k, _ in conv], list(douts) + list(couts)):
+                _, wi, bi, _, _ = layers[k]
                 final[wi] = w
                 if bi is not None:
                     final[bi] = b

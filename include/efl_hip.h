@@ -872,6 +872,65 @@ int efl_dp_dense_clip_sum(const efl_dp_dense* layers, int64_t nlayers, int64_t B
                           int clip_mode, float l2_norm_clip, int mode, float sigma, float divisor,
                           uint64_t seed, float* scales, double* work, int64_t work_elems, void* stream);
 
+/* The pieces of the two steps above for a model whose variables are not all of one kind: every family
+ * writes its per-microbatch partial sums of squares into ONE work buffer [rows, slots] (row i's slots
+ * at work + i * slots, a family's own at [slot0, slot0 + its count)), efl_dp_scales turns the rows
+ * into the clip scales, and every family's sum then runs with clip_mode 2.
+ * efl_dp_dense_sqnorm: k_dp_dense_sqnorm of efl_dp_dense_clip_sum, one slot per layer (nlayers slots).
+ * efl_dp_scales: scales[i] = (float)(clip * min(1 / sqrt(S_i), 1 / clip)), S_i = row i's slots summed in
+ * double in a fixed order (S_i = 0 gives 1). Both check their arguments as efl_dp_dense_clip_sum does
+ * (EFL_E_INVALID_ARGUMENT before any HIP call; slot0 < 0 or slot0 + count > slots included). */
+int efl_dp_dense_sqnorm(const efl_dp_dense* layers, int64_t nlayers, int64_t B, int64_t rows, double* work,
+                        int64_t slot0, int64_t slots, void* stream);
+int efl_dp_scales(const double* work, int64_t slots, int64_t rows, float l2_norm_clip, float* scales, void* stream);
+
+/* The same step for Conv2d layers (groups = 1, zero padding) WITHOUT the stacked gradients
+ * (csrc/dpconv.hip). A layer gives its input x [B, cin, h, w] and d [B, cout, ho, wo], the gradient of
+ * the summed loss with respect to its output, both contiguous NCHW; microbatch m is the r = B / rows
+ * consecutive examples from m r, 1 <= r <= 16. With T = ho wo, K = cin kh kw, q = (c kh + i) kw + j and
+ *   U[b][t][q] = x[b][c][oy sh - ph + i dh][ox sw - pw + j dw]   (0 outside the image),
+ * G_m [cout, K] = sum_{a in m} sum_t d[a][.][t] (x) U[a][t][.] (weight.grad in torch's layout) and
+ * g_m[o] = sum_{a, t} d[a][o][t].
+ * Rounding contract.
+ *   Scales: S_m = sum over layers of ||G_m||_F^2 (+ ||g_m||^2 with a bias), G_m formed on chip in double
+ *   (v_mfma_f64_16x16x4_f64 over exactly widened fp32 operands) in a fixed order, never stored; scale =
+ *   (float)(clip * min(1 / sqrt(S_m), 1 / clip)) rounded once; S_m = 0 gives 1.
+ *   Sum: s d rounded once, then fp32 accumulation on v_mfma_f32_32x32x2_f32 in a fixed order within a
+ *   split, the splits added in order, then efl_dp_noise's noise and division (through efl_dp_clip_sum,
+ *   clip_mode 0, over the partials). Per element |got - exact| <= (B T + 3) 2^-24 (sum_{b,t} |s d u| + |noise|)
+ *   / |divisor| (the bias: sum |s d|). The same inputs give the same bytes, on any device: the reduction
+ *   is split into min(rows, 16) groups of ceil(rows / min(rows, 16)) consecutive microbatches (the last
+ *   group ragged, empty groups dropped), a function of `rows` alone.
+ * w_out [cout, cin, kh, kw] and b_out [cout] (NULL: no bias, nothing of it enters S_m) are 16-byte
+ * aligned; element j of each takes normal j % 4 of block ctr0_w / ctr0_b + j / 4 under `seed`.
+ * efl_dp_conv_work_elems: doubles of `work` (rows x the layers' 32 x 32 blocks of the [cout, K] plane;
+ * clip_mode 1 only). efl_dp_conv_partial_elems: floats of `partials` (always needed, 16-byte aligned).
+ * efl_dp_conv_sqnorm writes the layers' slots [slot0, slot0 + efl_dp_conv_work_elems / rows) of a
+ * shared work buffer (above). clip_mode, l2_norm_clip, mode, sigma, divisor, seed and scales are
+ * efl_dp_dense_clip_sum's. `layers` is a HOST array; it travels to the kernels by value, 24 layers per
+ * launch. The outputs and the scratch must not overlap the inputs. nlayers == 0 is a no-op.
+ * EFL_E_INVALID_ARGUMENT, before any HIP call, for: what efl_dp_dense_clip_sum refuses; a size, stride
+ * or dilation < 1 or a padding < 0; ho / wo that are not floor((h + 2 ph - dh (kh - 1) - 1) / sh) + 1 (and
+ * so for w); a null x / d / w_out; a w_out or b_out that is not 16-byte aligned; a kernel so dilated
+ * that one output position's input window over the channels of 32 weights passes 8,192 floats; a
+ * null, misaligned or short partials. */
+typedef struct efl_dp_conv {
+  const float* x;                          /* [B, cin, h, w]                */
+  const float* d;                          /* [B, cout, ho, wo]             */
+  float* w_out;                            /* [cout, cin, kh, kw]           */
+  float* b_out;                            /* [cout] or NULL (no bias)      */
+  int32_t cin, h, w, cout, ho, wo, kh, kw, sh, sw, ph, pw, dh, dw;
+  uint64_t ctr0_w, ctr0_b;                 /* first Philox block of each    */
+} efl_dp_conv;
+int64_t efl_dp_conv_work_elems(const efl_dp_conv* layers, int64_t nlayers, int64_t rows);
+int64_t efl_dp_conv_partial_elems(const efl_dp_conv* layers, int64_t nlayers, int64_t B, int64_t rows);
+int efl_dp_conv_sqnorm(const efl_dp_conv* layers, int64_t nlayers, int64_t B, int64_t rows, double* work,
+                       int64_t slot0, int64_t slots, void* stream);
+int efl_dp_conv_clip_sum(const efl_dp_conv* layers, int64_t nlayers, int64_t B, int64_t rows, int clip_mode,
+                         float l2_norm_clip, int mode, float sigma, float divisor, uint64_t seed,
+                         float* scales, double* work, int64_t work_elems, float* partials,
+                         int64_t partial_elems, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,8 +8,9 @@
            around compute_gradients that ends in a device synchronise, `--rounds` interleaved rounds
            after a warm-up, the median reported. The two results are compared first.
            --model criteo_mlp (the criteo leader's dense stack, 181 -> 64 -> 16 -> 2) or wide_mlp
-           (1024 -> 1024 -> 1024 -> 10) times microbatch_gradients="factored" (csrc/dpdense.hip)
-           beside the two, with each path's peak device memory over a step.
+           (1024 -> 1024 -> 1024 -> 10) takes those instead. microbatch_gradients="factored" is timed
+           beside the two (csrc/dpdense.hip for the Linear modules, csrc/dpconv.hip for dp_cnn's Conv2d
+           modules), with each path's peak device memory over a step.
   kernels  efl_dp_clip_sum alone at [256, 1 Mi] float32 (clip mode 1: the norm pass reads the stack
            once, the sum pass once more; clip mode 0: one read), HIP events around `--inner` calls,
            as a fraction of the 8 TB/s HBM peak: algorithmic bytes (reads of the stack + one write of
@@ -35,6 +36,8 @@ ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--inner", type=int, default=20)
 ap.add_argument("--batch", type=int, default=256)
 ap.add_argument("--model", choices=["dp_cnn", "criteo_mlp", "wide_mlp"], default="dp_cnn")
+ap.add_argument("--paths", default="loop,batched,factored",
+                help="the microbatch_gradients paths to time, the first the one the others are compared with")
 ap.add_argument("--no-kernels", action="store_true", help="skip the efl_dp_clip_sum kernel measurement")
 ap.add_argument("--kernel-shape", type=int, nargs=2, default=[256, 1 << 20])
 ap.add_argument("--out", default=None)
@@ -61,12 +64,11 @@ model = nn.Sequential(nn.Conv2d(1, 16, 8, stride=2, padding=3), nn.ReLU(), nn.Ma
                       nn.Conv2d(16, 32, 4, stride=2), nn.ReLU(), nn.MaxPool2d(2, 1), nn.Flatten(),
                       nn.Linear(512, 32), nn.ReLU(), nn.Linear(32, 10)).to(dev)
 x = torch.randn(args.batch, 1, 28, 28, device=dev)
-paths = ("loop", "batched")
+paths = tuple(args.paths.split(","))
 if args.model != "dp_cnn":
     widths = (181, 64, 16, 2) if args.model == "criteo_mlp" else (1024, 1024, 1024, 10)
     model = nn.Sequential(*[m for i, o in zip(widths, widths[1:]) for m in (nn.Linear(i, o), nn.ReLU())][:-1]).to(dev)
     x = torch.randn(args.batch, widths[0], device=dev)
-    paths += ("factored",)
 # "factored" counts the forward passes of its layers between steps: it gets a copy of the model
 import copy  # noqa: E402
 models = {p: copy.deepcopy(model) if p == "factored" else model for p in paths}
@@ -75,6 +77,8 @@ y = torch.randint(0, model[-1].out_features, (args.batch,), device=dev)
 opts = {p: efl.privacy.DPGradientDescentGaussianOptimizer(list(models[p].parameters()), noise_multiplier=1.0,
                                                           l2_norm_clip=1.0, learning_rate=0.25, microbatch_gradients=p,
                                                           dense_layers=[m for m in models[p] if isinstance(m, nn.Linear)]
+                                                          if p == "factored" else None,
+                                                          conv_layers=[m for m in models[p] if isinstance(m, nn.Conv2d)]
                                                           if p == "factored" else None)
         for p in paths}
 
@@ -93,8 +97,8 @@ for p in opts:
     efl.privacy.set_noise_seed(5, 0)
     grads[p] = step(p)[1]
 # same noise positions; the sums differ by the scales' rounding (fp32 reductions against double)
-diff = max(float((a - b).abs().max() / (b.abs().max() + 1e-30)) for p in paths[1:]
-           for a, b in zip(grads[p], grads["loop"]))
+diff = max([float((a - b).abs().max() / (b.abs().max() + 1e-30)) for p in paths[1:]
+            for a, b in zip(grads[p], grads[paths[0]])], default=0.0)
 assert diff < 1e-4, diff
 del grads
 peak = {}
@@ -112,8 +116,9 @@ emit({"bench": "dp_step_compute_gradients", "model": args.model, "batch": args.b
       "variables": len(params), "floats": sum(p.numel() for p in params), "rounds": args.rounds,
       "ms_per_step": {p: round(v, 3) for p, v in med.items()},
       "ms_min_max": {p: [round(min(t), 3), round(max(t), 3)] for p, t in times.items()},
-      "peak_bytes": peak, "loop_over_batched": round(med["loop"] / med["batched"], 2),
-      **({"batched_over_factored": round(med["batched"] / med["factored"], 2)} if "factored" in med else {}),
+      "peak_bytes": peak,
+      **({"loop_over_batched": round(med["loop"] / med["batched"], 2)} if "loop" in med and "batched" in med else {}),
+      **({"batched_over_factored": round(med["batched"] / med["factored"], 2)} if "batched" in med and "factored" in med else {}),
       "max_rel_diff": diff})
 if args.no_kernels:
     sys.exit(0)
