@@ -376,52 +376,7 @@ __global__ __launch_bounds__(kBlock) void k_mask_rows(const float* __restrict__ 
 // normals<NB>: k_dp_noise then compiles to the same instructions (with an array argument the
 // compiler no longer narrowed the last Philox round of the words whose low 23 bits alone are used;
 // with a callable that captures by reference the NB = 1 instances changed). DESIGN.md §5c.
-template <int NB, bool KEEP = false, class WORDS>
-__device__ __forceinline__ void box_muller_staged(WORDS words, float (&z)[NB][4], bm_stages* st = nullptr) {
-  constexpr int P = 2 * NB;
-  uint32_t c[NB][4];
-  words(c);
-  float u1[P], v1[P], r[P], tl[P], sn[P], cs[P];
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    u1[p] = u01(c[p >> 1][(p & 1) * 2]);
-    v1[p] = efl_box_muller_angle(u01(c[p >> 1][(p & 1) * 2 + 1]));
-  }
-#pragma unroll
-  for (int p = 0; p < P; ++p) r[p] = log_unit(fmaxf(u1[p], 1.0e-7f), tl[p]);
-#pragma unroll
-  for (int p = 0; p < P; ++p) r[p] = radius_unit(r[p], tl[p]);
-#pragma unroll
-  for (int p = 0; p < P; ++p) r[p] = u1[p] < 1.0e-7f ? __uint_as_float(kRClampBits) : r[p];
-#pragma unroll
-  for (int p = 0; p < P; ++p) efl_sincos_angle(v1[p], &sn[p], &cs[p]);
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    z[p >> 1][(p & 1) * 2] = sn[p] * r[p];
-    z[p >> 1][(p & 1) * 2 + 1] = cs[p] * r[p];
-  }
-  if constexpr (KEEP) {
-#pragma unroll
-    for (int p = 0; p < P; ++p) st[p] = bm_stages{r[p], sn[p], cs[p]};
-  }
-}
-
-template <int NB>
-__device__ __forceinline__ void normals(uint64_t seed, uint64_t blk0, uint64_t stride, float (&z)[NB][4]) {
-  box_muller_staged<NB>(
-      [=](uint32_t (&c)[NB][4]) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-          const uint64_t blk = blk0 + (uint64_t)b * stride;
-          c[b][0] = (uint32_t)blk;
-          c[b][1] = (uint32_t)(blk >> 32);
-          c[b][2] = 0u;
-          c[b][3] = 0u;
-        }
-        pl::philox_n<NB>(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-      },
-      z);
-}
+// The two templates live in dp_normal.h, which csrc/dpembed.hip's noise pass shares.
 
 // One lane owns NB Philox blocks (4 elements each) kBlock lanes apart, so a wave's accesses stay
 // 64 x 16 contiguous bytes. Round 2 drew the normals first and then loaded x: every lane sat in

@@ -69,6 +69,12 @@ _SIGS = {
     "efl_dp_conv_sqnorm": ([_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp], _i32),
     "efl_dp_conv_clip_sum": ([_vp, _i64, _i64, _i64, _i32, ctypes.c_float, _i32, ctypes.c_float, ctypes.c_float,
                               ctypes.c_uint64, _vp, _vp, _i64, _vp, _i64, _vp], _i32),
+    # the same step for embedding tables from ids and output gradients: layers is a host array of DpEmbed
+    "efl_dp_embed_work_elems": ([_i64, _i64], _i64),
+    "efl_dp_embed_scratch_bytes": ([_vp, _i64, _i64], _i64),
+    "efl_dp_embed_sqnorm": ([_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp], _i32),
+    "efl_dp_embed_clip_sum": ([_vp, _i64, _i64, _i64, _i32, ctypes.c_float, _i32, ctypes.c_float, ctypes.c_float,
+                               ctypes.c_uint64, _vp, _vp, _i64, _vp, _i64, _vp], _i32),
     # RSA blind-signature PSI (efl.psi; include/efl_hip.h efl_rsa_*): contexts and info structs as void*
     "efl_rsa_ctx_create": ([_vp], _i32),
     "efl_rsa_ctx_destroy": ([_vp], _i32),
@@ -148,6 +154,18 @@ class DpConv(ctypes.Structure):
                 [(n, ctypes.c_int32) for n in ("cin", "h", "w", "cout", "ho", "wo", "kh", "kw", "sh", "sw", "ph", "pw",
                                                "dh", "dw")] +
                 [("ctr0_w", ctypes.c_uint64), ("ctr0_b", ctypes.c_uint64)])
+
+
+class DpEmbed(ctypes.Structure):
+    """efl_dp_embed (include/efl_hip.h): one embedding table of efl_dp_embed_clip_sum, the looked-up ids
+    [B, L], the gradient d of the summed loss by the layer's output (rows of dim floats, one per entry or
+    one per bag), the weight w of every entry and the [V, dim] output."""
+    _fields_ = [("ids", _vp), ("d", _vp), ("d_row_stride", _i64), ("d_l_stride", _i64), ("out", _vp), ("V", _i64),
+                ("dim", ctypes.c_int32), ("L", ctypes.c_int32), ("w", ctypes.c_float), ("ctr0", ctypes.c_uint64)]
+
+
+DP_EMBED_NOISE_TILE = 4096      # EFL_DP_EMBED_NOISE_TILE: elements of a table per workgroup of the noise pass
+DP_EMBED_MAX_ENTRIES = 8192     # B L of one layer: its sort keys fill the 64 KiB of LDS
 
 
 # TensorFlow DataType numbers (types.proto), as used by the C ABI and the wire format.

@@ -37,7 +37,12 @@ the same path through csrc/dpconv.hip's efl_dp_conv_clip_sum (`dp_conv_clip_sum_
 forms each microbatch's [Cout, Cin kh kw] gradient on chip in double and drops it, the sum is one implicit
 GEMM over all (example, output position) pairs. A model of both kinds clips under ONE norm: both families
 write their partial sums of squares into one buffer, one launch makes the scales, and both sums take them
-(`dp_factored_clip_sum_noise`). A model with any other variable is out of its scope.
+(`dp_factored_clip_sum_noise`). torch.nn.Embedding and torch.nn.EmbeddingBag (modes "sum" and "mean", 2-D
+input) tables given as `embedding_layers=` are the third family (csrc/dpembed.hip's efl_dp_embed_clip_sum,
+`dp_embed_clip_sum_noise`): a microbatch's gradient of a table is zero but for the rows its ids name, so the
+norm and the clipped sum come from a sort of the step's at most 8,192 (id, entry) keys per table and the
+entries' rows of d, and the only dense pass is the noise, one write of the table and no read. A recommender
+of tables and an MLP runs under one norm. A model with any other variable is out of its scope.
 
 Torch mapping. TF optimisers get their variables at minimize time; torch ones at construction.
 These classes take either: `params` (as `params=`, or first positional with the DP arguments as
@@ -99,6 +104,7 @@ def dp_noise(x: torch.Tensor, mode: int, sigma: float, divisor: float = 1.0, str
 MICROBATCH_GRADIENTS = ("loop", "batched")       # for any model and any query
 DENSE_MICROBATCH_GRADIENTS = ("factored",)        # for models of registered Linear layers (dense_layers=)
 MAX_ROWS_PER_MICROBATCH = 16                      # efl_dp_dense_clip_sum's limit on batch rows per microbatch
+MAX_EMBEDDING_ENTRIES = lib.DP_EMBED_MAX_ENTRIES  # efl_dp_embed_clip_sum's limit on looked-up ids per table and step
 _microbatch_gradients = "loop"
 
 
@@ -107,7 +113,9 @@ def set_microbatch_gradients(name: str) -> None:
     """The process default of the DP optimisers' `microbatch_gradients` keyword: "loop" (one
     autograd.grad and one torch clip-and-add per microbatch, the default), "batched" (one batched
     autograd.grad, then efl_dp_clip_sum over the stacked gradients) or "factored" (one ordinary
-    autograd.grad to the registered dense layers' outputs, then efl_dp_dense_clip_sum)."""
+    autograd.grad to the outputs of the layers registered as dense_layers=, conv_layers= and
+    embedding_layers=, then efl_dp_dense_clip_sum, efl_dp_conv_clip_sum and efl_dp_embed_clip_sum under one
+    shared clip norm; a model with any other variable is refused)."""
     global _microbatch_gradients
     _microbatch_gradients = _resolve_microbatch_gradients(name)
 
@@ -429,56 +437,169 @@ def dp_conv_clip_sum_noise(layers, rows: int, l2_norm_clip, mode: int, sigma: fl
     return outs
 
 
-def _factored_clip_sum(dense, conv, rows, l2_norm_clip, mode, sigma, divisor, seed, dctrs, cctrs, scales):
-    """Checked dense and conv layers under ONE norm: (dense outs, conv outs, scales | None). With both
-    families and no given scales, both write their norm slots into one work buffer [rows, slots] (the
-    dense layers' first), efl_dp_scales makes the scales, and both sums run with them (clip_mode 2)."""
-    dtab = ctab = None
-    if dense and conv and scales is None and l2_norm_clip is not None:
-        dev, B, raw, h = dense[0][0].device, dense[0][0].shape[0], lib.raw(), lib.stream_handle(dense[0][0].device)
-        dtab, ctab = _dense_table(dense, dctrs), _conv_table(conv, cctrs)
-        slots = len(dense) + _elems(raw.efl_dp_conv_work_elems(ctab[0], len(conv), rows)) // rows
+def _check_embed_layers(layers, rows, who):
+    """[(ids [B, L], d [B, L, dim] | [B, dim], num_embeddings, weight)] with detached tensors."""
+    out = []
+    for ids, d, V, weight in layers:
+        ids, d = lib.as_tensor(ids).detach(), lib.as_tensor(d).detach()
+        if ids.dtype.is_floating_point or ids.dtype.is_complex or ids.dtype == torch.bool:
+            raise errors.InvalidArgumentError(f"{who}: ids must have an integer dtype, got {ids.dtype}")
+        out.append((ids[:, None] if ids.dim() == 1 else ids, d, int(V), float(weight)))
+    dev, B = out[0][1].device, out[0][1].shape[0] if out[0][1].dim() else 0
+    for ids, d, V, _ in out:
+        if d.dtype != torch.float32:
+            raise errors.InvalidArgumentError(f"{who}: d must be float32, got {d.dtype}")
+        if ids.device != dev or d.device != dev or dev.type != "cuda":
+            raise errors.InvalidArgumentError(f"{who}: every ids and d lies on one ROCm device")
+        if (ids.dim() != 2 or d.dim() not in (2, 3) or ids.shape[0] != B or d.shape[0] != B or 0 in ids.shape
+                or 0 in d.shape or (d.dim() == 3 and d.shape[1] != ids.shape[1]) or V < 1):
+            raise errors.InvalidArgumentError(
+                f"{who}: a table takes ids [B, L] and d [B, L, dim] (an embedding) or [B, dim] (a bag) with B = {B} "
+                f"and at least one row, got {tuple(ids.shape)}, {tuple(d.shape)} and {V} rows")
+        if ids.numel() > MAX_EMBEDDING_ENTRIES:
+            raise errors.InvalidArgumentError(
+                f"{who}: {ids.numel()} ids looked up in one table, more than {MAX_EMBEDDING_ENTRIES} entries per layer")
+    rows = int(rows)
+    if rows < 1 or B % rows:
+        raise errors.InvalidArgumentError(f"{who}: {rows} microbatches do not divide the batch of {B}")
+    if B // rows > MAX_ROWS_PER_MICROBATCH:
+        raise errors.InvalidArgumentError(f"{who}: {B // rows} examples per microbatch, at most "
+                                          f"{MAX_ROWS_PER_MICROBATCH} (r > {MAX_ROWS_PER_MICROBATCH})")
+    return out, rows
+
+
+def _embed_table(layers, ctrs):
+    """The DpEmbed table of checked embedding layers with freshly carved outputs: (table, [table_grad],
+    tensors to keep alive)."""
+    dev = layers[0][1].device
+    outs = lib._carve([torch.empty(V, d.shape[-1], device="meta") for _, d, V, _ in layers], torch.float32, dev)
+    arr, keep = (lib.DpEmbed * len(layers))(), []
+    for rec, (ids, d, V, weight), ctr0, out in zip(arr, layers, ctrs, outs):
+        ids, d = ids.to(torch.int64).contiguous(), d.contiguous()
+        keep += [ids, d]
+        L, dim = ids.shape[1], d.shape[-1]
+        rec.ids, rec.d, rec.out, rec.V, rec.dim, rec.L, rec.w, rec.ctr0 = ids.data_ptr(), d.data_ptr(), out.data_ptr(), V, dim, L, weight, ctr0
+        rec.d_row_stride, rec.d_l_stride = (L * dim, dim) if d.dim() == 3 else (dim, 0)
+    return arr, outs, keep
+
+
+def _embed_clip_sum(layers, rows, l2_norm_clip, mode, sigma, divisor, seed, ctrs, scales, table=None):
+    """efl_dp_embed_clip_sum over checked layers; ctrs: per table its first Philox block; table: their
+    _embed_table when the caller has made it. Returns ([table_grad], scales | None)."""
+    dev, B, raw = layers[0][1].device, layers[0][1].shape[0], lib.raw()
+    arr, outs, keep = table or _embed_table(layers, ctrs)
+    clip_mode = 2 if scales is not None else 0 if l2_norm_clip is None else 1
+    work, work_elems = None, 0
+    if clip_mode == 2:
+        scales = lib.as_tensor(scales).detach().to(dev, torch.float32).contiguous()
+        if scales.shape != (rows,):
+            raise errors.InvalidArgumentError(f"dp_embed_clip_sum_noise: scales must be [{rows}]")
+    elif clip_mode == 1:
+        work_elems = _elems(raw.efl_dp_embed_work_elems(len(layers), rows))
+        work = torch.empty(max(work_elems, 1), dtype=torch.float64, device=dev)
+        scales = torch.empty(rows, dtype=torch.float32, device=dev)
+    nbytes = _elems(raw.efl_dp_embed_scratch_bytes(arr, len(layers), B))
+    scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    lib.check(raw.efl_dp_embed_clip_sum(arr, len(layers), B, rows, clip_mode, float(l2_norm_clip or 0.0), int(mode),
+                                        float(sigma), float(divisor), seed,
+                                        None if scales is None else scales.data_ptr(),
+                                        None if work is None else work.data_ptr(), work_elems, scratch.data_ptr(),
+                                        nbytes, lib.stream_handle(dev)))
+    return outs, scales
+
+
+@exporter.export("privacy.dp_embed_clip_sum_noise")
+def dp_embed_clip_sum_noise(layers, rows: int, l2_norm_clip, mode: int, sigma: float, divisor: float = 1.0,
+                            stream: NoiseStream | None = None, scales=None, return_scales: bool = False):
+    """efl_dp_embed_clip_sum: a DP-SGD step's clipped, summed, noised and divided gradients of embedding
+    tables from the looked-up ids and the output gradients, without a dense gradient per microbatch.
+    `layers` is a list of (ids [B, L] or [B], d, num_embeddings, weight): ids of an integer dtype, d the
+    float32 gradient of the SUM of the per-example losses by the layer's output, [B, L, dim] for a
+    torch.nn.Embedding and [B, dim] for a torch.nn.EmbeddingBag (which decides the kind), weight the factor
+    of every entry (1; 1 / L for a bag of mode "mean"). At most 8,192 ids per table; an id outside
+    [0, num_embeddings) hits no row. Microbatch i is the B / rows (at most 16) consecutive examples from
+    i * B / rows. Returns [table_grad [num_embeddings, dim], ...]; mode, sigma, divisor, scales,
+    return_scales and the stream positions (one take(numel) per table, in layer order) are
+    dp_dense_clip_sum_noise's. A row no id names is the noise of zero."""
+    layers = list(layers)
+    if not layers:
+        return ([], None) if return_scales else []
+    layers, rows = _check_embed_layers(layers, rows, "dp_embed_clip_sum_noise")
+    st = stream or _stream
+    takes = [st.take(V * d.shape[-1]) for _, d, V, _ in layers]
+    outs, scales = _embed_clip_sum(layers, rows, l2_norm_clip, mode, sigma, divisor, takes[0][0], [t[1] for t in takes], scales)
+    if return_scales:
+        return outs, torch.ones(rows, device=layers[0][1].device) if scales is None else scales
+    return outs
+
+
+def _factored_clip_sum(dense, conv, rows, l2_norm_clip, mode, sigma, divisor, seed, dctrs, cctrs, scales,
+                       embed=(), ectrs=()):
+    """Checked dense, conv and embedding layers under ONE norm: (dense outs, conv outs, embedding outs,
+    scales | None). With more than one family and no given scales, all write their norm slots into one work
+    buffer [rows, slots] (dense, then conv, then embedding), efl_dp_scales makes the scales, and every sum
+    runs with them (clip_mode 2)."""
+    dtab = ctab = etab = None
+    if (bool(dense) + bool(conv) + bool(embed)) > 1 and scales is None and l2_norm_clip is not None:
+        first = dense[0][0] if dense else conv[0][0]
+        dev, B, raw, h = first.device, first.shape[0], lib.raw(), lib.stream_handle(first.device)
+        dtab, ctab, etab = dense and _dense_table(dense, dctrs), conv and _conv_table(conv, cctrs), embed and _embed_table(embed, ectrs)
+        nc = _elems(raw.efl_dp_conv_work_elems(ctab[0], len(conv), rows)) // rows if conv else 0
+        slots = len(dense) + nc + len(embed)
         work = torch.empty(rows * slots, dtype=torch.float64, device=dev)
         scales = torch.empty(rows, dtype=torch.float32, device=dev)
-        lib.check(raw.efl_dp_dense_sqnorm(dtab[0], len(dense), B, rows, work.data_ptr(), 0, slots, h))
-        lib.check(raw.efl_dp_conv_sqnorm(ctab[0], len(conv), B, rows, work.data_ptr(), len(dense), slots, h))
+        if dense:
+            lib.check(raw.efl_dp_dense_sqnorm(dtab[0], len(dense), B, rows, work.data_ptr(), 0, slots, h))
+        if conv:
+            lib.check(raw.efl_dp_conv_sqnorm(ctab[0], len(conv), B, rows, work.data_ptr(), len(dense), slots, h))
+        if embed:
+            lib.check(raw.efl_dp_embed_sqnorm(etab[0], len(embed), B, rows, work.data_ptr(), len(dense) + nc, slots, h))
         lib.check(raw.efl_dp_scales(work.data_ptr(), slots, rows, float(l2_norm_clip), scales.data_ptr(), h))
-    douts = couts = []
+    douts = couts = eouts = []
     if dense:                               # one family alone takes its own norm pass (clip_mode 1)
-        douts, scales = _dense_clip_sum(dense, rows, l2_norm_clip, mode, sigma, divisor, seed, dctrs, scales, dtab)
+        douts, scales = _dense_clip_sum(dense, rows, l2_norm_clip, mode, sigma, divisor, seed, dctrs, scales, dtab or None)
     if conv:
-        couts, scales = _conv_clip_sum(conv, rows, l2_norm_clip, mode, sigma, divisor, seed, cctrs, scales, ctab)
-    return douts, couts, scales
+        couts, scales = _conv_clip_sum(conv, rows, l2_norm_clip, mode, sigma, divisor, seed, cctrs, scales, ctab or None)
+    if embed:
+        eouts, scales = _embed_clip_sum(embed, rows, l2_norm_clip, mode, sigma, divisor, seed, ectrs, scales, etab or None)
+    return douts, couts, eouts, scales
 
 
 @exporter.export("privacy.dp_factored_clip_sum_noise")
 def dp_factored_clip_sum_noise(dense_layers, conv_layers, rows: int, l2_norm_clip, mode: int, sigma: float,
                                divisor: float = 1.0, stream: NoiseStream | None = None, scales=None,
-                               return_scales: bool = False):
-    """dp_dense_clip_sum_noise and dp_conv_clip_sum_noise over one model's layers under ONE shared clip
-    norm: scale_i = clip * min(1 / ||g_i||, 1 / clip) with g_i microbatch i's gradient of ALL the layers'
-    variables. `dense_layers` and `conv_layers` are those functions' lists (either may be empty); the
-    dense variables come first in the stream. Returns (dense_outs, conv_outs), and the scales after them
-    with return_scales."""
-    dense, conv = list(dense_layers), list(conv_layers)
+                               return_scales: bool = False, *, embedding_layers=None):
+    """dp_dense_clip_sum_noise, dp_conv_clip_sum_noise and dp_embed_clip_sum_noise over one model's layers
+    under ONE shared clip norm: scale_i = clip * min(1 / ||g_i||, 1 / clip) with g_i microbatch i's gradient
+    of ALL the layers' variables. `dense_layers`, `conv_layers` and `embedding_layers` (keyword only) are
+    those functions' lists (any may be empty); the dense variables come first in the stream, then the conv
+    ones, then the tables. Returns (dense_outs, conv_outs), with `embedding_layers` given (dense_outs,
+    conv_outs, embedding_outs), and the scales after them with return_scales."""
+    dense, conv, embed = list(dense_layers), list(conv_layers), list(embedding_layers or ())
     who = "dp_factored_clip_sum_noise"
-    if not dense and not conv:
-        return ([], [], None) if return_scales else ([], [])
+    tail = () if embedding_layers is None else ([],)
+    if not dense and not conv and not embed:
+        return ([], [], *tail, None) if return_scales else ([], [], *tail)
     if dense:
         dense, rows = _check_dense_layers(dense, rows, who)
     if conv:
         conv, rows = _check_conv_layers(conv, rows, who)
-    if dense and conv and (dense[0][0].shape[0] != conv[0][0].shape[0] or dense[0][0].device != conv[0][0].device):
-        raise errors.InvalidArgumentError(f"{who}: the dense and the conv layers take one batch on one device")
+    if embed:
+        embed, rows = _check_embed_layers(embed, rows, who)
+    firsts = [f[0][0] for f in (dense, conv, embed) if f]
+    if any(t.shape[0] != firsts[0].shape[0] or t.device != firsts[0].device for t in firsts):
+        raise errors.InvalidArgumentError(f"{who}: the dense, conv and embedding layers take one batch on one device")
     st = stream or _stream
     seed, dctrs = _take_layers([(d.shape[1] * x.shape[1], d.shape[1] if b else 0) for x, d, b in dense], st)
     seed_c, cctrs = _take_layers(_conv_numels(conv), st)
-    douts, couts, scales = _factored_clip_sum(dense, conv, rows, l2_norm_clip, mode, sigma, divisor,
-                                              seed if seed is not None else seed_c, dctrs, cctrs, scales)
+    seed_e, ectrs = _take_layers([(V * d.shape[-1], 0) for _, d, V, _ in embed], st)
+    seed = next(v for v in (seed, seed_c, seed_e) if v is not None)
+    douts, couts, eouts, scales = _factored_clip_sum(dense, conv, rows, l2_norm_clip, mode, sigma, divisor, seed, dctrs,
+                                                     cctrs, scales, embed, [c for c, _ in ectrs])
+    outs = (douts, couts) if embedding_layers is None else (douts, couts, eouts)
     if return_scales:
-        dev = (dense or conv)[0][0].device
-        return douts, couts, torch.ones(rows, device=dev) if scales is None else scales
-    return douts, couts
+        return (*outs, torch.ones(rows, device=firsts[0].device) if scales is None else scales)
+    return outs
 
 
 def _fusable(query, cls, stacked):
@@ -627,9 +748,9 @@ def make_optimizer_class(cls):
             """(dp_sum_query, num_microbatches=None, unroll_microbatches=False, [params], **opt
             kwargs), or torch style (params, dp_sum_query=..., ...). microbatch_gradients= "loop" /
             "batched" / "factored" (keyword only; None: the process default, set_microbatch_gradients).
-            dense_layers= and conv_layers= (keyword only): the torch.nn.Linear and torch.nn.Conv2d
-            modules "factored" takes its gradients from; each gets a forward hook that keeps its input
-            and output of the current step."""
+            dense_layers=, conv_layers= and embedding_layers= (keyword only): the torch.nn.Linear, the
+            torch.nn.Conv2d and the torch.nn.Embedding / torch.nn.EmbeddingBag modules "factored" takes its
+            gradients from; each gets a forward hook that keeps its input and output of the current step."""
             self._microbatch_gradients = kwargs.pop("microbatch_gradients", None)
             _resolve_microbatch_gradients(self._microbatch_gradients)
             self._dense = {}                # Linear module -> [(detached input, output)] since the last step
@@ -651,6 +772,22 @@ def make_optimizer_class(cls):
                 _conv_padding(layer.padding, layer.kernel_size, layer.dilation, "conv_layers")
                 self._conv[layer] = []
                 layer.register_forward_hook(self._keep_dense)
+            self._embed = {}                # Embedding / EmbeddingBag module -> [(ids, output, plain call)]
+            for layer in kwargs.pop("embedding_layers", None) or ():
+                if not isinstance(layer, (torch.nn.Embedding, torch.nn.EmbeddingBag)):
+                    raise errors.InvalidArgumentError(
+                        f"embedding_layers takes torch.nn.Embedding and torch.nn.EmbeddingBag modules, got "
+                        f"{type(layer).__name__}")
+                for name, plain in (("padding_idx", None), ("max_norm", None), ("scale_grad_by_freq", False), ("sparse", False)):
+                    if getattr(layer, name) is not plain and getattr(layer, name) != plain:
+                        raise errors.InvalidArgumentError(
+                            f"embedding_layers takes tables without {name}, got {name}={getattr(layer, name)!r}")
+                if getattr(layer, "mode", "sum") not in ("sum", "mean"):
+                    raise errors.InvalidArgumentError(
+                        f'embedding_layers takes bags of mode "sum" or "mean", got mode {layer.mode!r} (a max has no '
+                        f"weighted sum of rows)")
+                self._embed[layer] = []
+                layer.register_forward_hook(self._keep_embed, with_kwargs=True)
             if "learning_rate" in kwargs:
                 kwargs["lr"] = kwargs.pop("learning_rate")
             lead = _as_params(args[0]) if args else None
@@ -707,7 +844,7 @@ def make_optimizer_class(cls):
                     return list(zip(self._factored_gradients(loss, var_list, grad_loss, reduce_func, params, nm,
                                                              batch_size), var_list))
                 finally:                    # the kept inputs and outputs belong to this step alone
-                    for seen in (*self._dense.values(), *self._conv.values()):
+                    for seen in (*self._dense.values(), *self._conv.values(), *self._embed.values()):
                         seen.clear()
             if path == "batched":
                 stacked = self._stacked_gradients(loss, var_list, grad_loss, reduce_func)
@@ -758,10 +895,18 @@ def make_optimizer_class(cls):
                     and _resolve_microbatch_gradients(self._microbatch_gradients) == "factored"):
                 (self._dense if layer in self._dense else self._conv)[layer].append((inputs[0].detach(), output))
 
+        def _keep_embed(self, layer, inputs, kwargs, output):
+            if (torch.is_grad_enabled() and output.requires_grad
+                    and _resolve_microbatch_gradients(self._microbatch_gradients) == "factored"):
+                rest = dict(kwargs)         # the ids come first or as input=; anything else set is refused later
+                ids = inputs[0] if inputs else rest.pop("input")
+                plain = all(a is None for a in (*inputs[1:], *rest.values()))
+                self._embed[layer].append((ids.detach(), output, plain))
+
         def _factored_gradients(self, loss, var_list, grad_loss, reduce_func, params, nm, batch):
-            """The step's gradients of the registered dense and conv layers' variables from ONE ordinary
-            backward to the layers' outputs, then efl_dp_dense_clip_sum (csrc/dpdense.hip) and
-            efl_dp_conv_clip_sum (csrc/dpconv.hip) under one shared norm. Precondition that cannot be
+            """The step's gradients of the registered dense, conv and embedding layers' variables from ONE
+            ordinary backward to the layers' outputs, then efl_dp_dense_clip_sum (csrc/dpdense.hip),
+            efl_dp_conv_clip_sum (csrc/dpconv.hip) and efl_dp_embed_clip_sum (csrc/dpembed.hip) under one shared norm. Precondition that cannot be
             checked here: the examples are independent in the forward pass (no batch statistics), so
             that row k of d(sum of the loss)/d(output) is example k's own."""
             who = 'microbatch_gradients="factored"'
@@ -773,28 +918,38 @@ def make_optimizer_class(cls):
             if callable(reduce_func):
                 raise errors.InvalidArgumentError(f"{who}: a callable REDUCE needs the per-microbatch losses")
             owner = {}
-            for layer in (*self._dense, *self._conv):
+            for layer in (*self._dense, *self._conv, *self._embed):
                 owner[layer.weight] = (layer, 0)
-                if layer.bias is not None:
+                if getattr(layer, "bias", None) is not None:
                     owner[layer.bias] = (layer, 1)
             used = {}                           # layer -> [index of its weight in var_list, of its bias]
             for i, v in enumerate(var_list):
                 if v not in owner:
                     raise errors.InvalidArgumentError(
                         f"{who}: variable {i} of var_list {tuple(v.shape)} is not the weight or bias of a layer "
-                        f"given as dense_layers= or conv_layers=")
+                        f"given as dense_layers=, conv_layers= or embedding_layers=")
                 used.setdefault(owner[v][0], [None, None])[owner[v][1]] = i
             layers = []
             for layer, (wi, bi) in used.items():
                 if wi is None:
                     raise errors.InvalidArgumentError(f"{who}: the bias of {layer} is in var_list without its weight")
                 is_conv = layer in self._conv
-                seen = (self._conv if is_conv else self._dense)[layer]
+                seen = (self._embed if layer in self._embed else self._conv if is_conv else self._dense)[layer]
                 if len(seen) != 1:
                     raise errors.InvalidArgumentError(
                         f"{who}: {layer} ran {len(seen)} times since the last step; each layer runs once")
-                x, out = seen[0]
-                if (x.dim() != (4 if is_conv else 2) or x.shape[0] != batch or x.dtype != torch.float32
+                x, out = seen[0][:2]
+                if layer in self._embed:
+                    bag = isinstance(layer, torch.nn.EmbeddingBag)
+                    if not seen[0][2] or (bag and x.dim() != 2):
+                        raise errors.InvalidArgumentError(
+                            f"{who}: {layer} takes its ids alone, a bag as a 2-D [B, L] input: offsets (a 1-D input) "
+                            f"and per_sample_weights are not supported")
+                    if x.dim() not in (1, 2) or x.shape[0] != batch or out.dtype != torch.float32:
+                        raise errors.InvalidArgumentError(
+                            f"{who}: {layer} takes [B] or [B, L] ids with B = {batch} per-example losses and gives "
+                            f"float32, got {tuple(x.shape)} and {out.dtype}")
+                elif (x.dim() != (4 if is_conv else 2) or x.shape[0] != batch or x.dtype != torch.float32
                         or out.dtype != torch.float32):
                     raise errors.InvalidArgumentError(
                         f"{who}: {layer} takes a float32 {'[B, Cin, H, W]' if is_conv else '[B, in]'} input with "
@@ -802,14 +957,19 @@ def make_optimizer_class(cls):
                 layers.append((layer, wi, bi, x, out))
             go = torch.ones_like(loss) if grad_loss is None else grad_loss.reshape(loss.shape)
             ds = torch.autograd.grad(loss, [l[4] for l in layers], grad_outputs=go, retain_graph=True, allow_unused=True)
-            dense, conv = [], []                # (position in `layers`, record)
+            dense, conv, embed = [], [], []     # (position in `layers`, record)
             for k, ((layer, _, bi, x, out), d) in enumerate(zip(layers, ds)):
                 d = d if d is not None else torch.zeros_like(out)
-                if layer in self._conv:
+                if layer in self._embed:
+                    mean = getattr(layer, "mode", "sum") == "mean"
+                    embed.append((k, (x, d, layer.num_embeddings, 1.0 / x.shape[1] if mean else 1.0)))
+                elif layer in self._conv:
                     conv.append((k, (x, d, bi is not None, layer.kernel_size, layer.stride, layer.padding, layer.dilation)))
                 else:
                     dense.append((k, (x, d, bi is not None)))
-            drecs, crecs = [r for _, r in dense], [r for _, r in conv]
+            drecs, crecs, erecs = [r for _, r in dense], [r for _, r in conv], [r for _, r in embed]
+            if erecs:
+                erecs, nm = _check_embed_layers(erecs, nm, who)
             if drecs:
                 drecs, nm = _check_dense_layers(drecs, nm, who)
             if crecs:
@@ -817,10 +977,11 @@ def make_optimizer_class(cls):
             takes = [_stream.take(v.numel()) for v in var_list]          # as the loop: var_list order
             ctr = [(takes[wi][1], takes[bi][1] if bi is not None else 0) for _, wi, bi, _, _ in layers]
             clip, mode, sigma = (params, 1, q._stddev) if type(q) is GaussianSumQuery else (None, 0, q._noise_multiplier)
-            douts, couts, _ = _factored_clip_sum(drecs, crecs, nm, clip, mode, sigma, float(nm), takes[0][0],
-                                                 [ctr[k] for k, _ in dense], [ctr[k] for k, _ in conv], None)
+            douts, couts, eouts, _ = _factored_clip_sum(drecs, crecs, nm, clip, mode, sigma, float(nm), takes[0][0],
+                                                        [ctr[k] for k, _ in dense], [ctr[k] for k, _ in conv], None,
+                                                        erecs, [ctr[k][0] for k, _ in embed])
             final = [None] * len(var_list)
-            for k, (w, b) in zip([k for k, _ in dense] + [k for k, _ in conv], list(douts) + list(couts)):
+            for k, (w, b) in zip([k for k, _ in dense + conv + embed], [*douts, *couts, *((t, None) for t in eouts)]):
                 _, wi, bi, _, _ = layers[k]
                 final[wi] = w
                 if bi is not None:

@@ -931,6 +931,60 @@ int efl_dp_conv_clip_sum(const efl_dp_conv* layers, int64_t nlayers, int64_t B, 
                          float* scales, double* work, int64_t work_elems, float* partials,
                          int64_t partial_elems, void* stream);
 
+/* The same step for embedding tables (torch.nn.Embedding; torch.nn.EmbeddingBag, modes "sum" and "mean")
+ * WITHOUT a dense per-microbatch gradient (csrc/dpembed.hip). A layer gives the looked-up ids [B, L]
+ * (int64, contiguous) and d, the gradient of the summed loss with respect to its output: entry e = b L + l
+ * has id ids[e] and gradient row d_e = d + b d_row_stride + l d_l_stride (dim floats). An Embedding's
+ * output is [B, L, dim] (d_l_stride = dim); a bag's is [B, dim] (d_l_stride = 0: its L entries share the
+ * row). w is the weight of every entry: 1, or (float)(1 / L) for mode "mean". Microbatch m is the
+ * r = B / rows consecutive examples from m r, 1 <= r <= 16; B L <= 8,192 entries per layer.
+ * NOTHING IS ADDRESSED BY AN ID: ids are sort keys and only take part in comparisons, so an id outside
+ * [0, V) cannot cause an out-of-range access. It matches no table row: it enters neither the norm nor
+ * the sum.
+ * Rounding contract.
+ *   Scales: S_m = sum over layers of sum over distinct v of || sum_{e in m, id_e = v} (double) w (double) d_e ||^2,
+ *   every run added in entry order, the runs reduced in a fixed order (no atomics: the same bytes on
+ *   every run); scale = (float)(clip * min(1 / sqrt(S_m), 1 / clip)) rounded once; S_m = 0 gives 1.
+ *   Sum: row v of the table takes, in fp32 from 0.0f and in entry order (which is microbatch order: the
+ *   loop's `sum = sum + g_m s_m` on the rows that are hit), acc = acc + t_e d_e[c], the product and the
+ *   sum each rounded on their own, t_e = s_{m(e)} w rounded once (s itself when w = 1; w itself in
+ *   clip_mode 0); then efl_dp_noise's noise and division. Per element, with n_v the number of entries
+ *   that hit row v: |got - exact| <= (n_v + 3) 2^-24 (sum |t d| + |noise|) / |divisor|. A row that is not
+ *   hit is exactly the noise of 0.0f, (0 + n) / divisor with n = (z * 0) * sigma or z * sigma + 0.
+ * out [V, dim] is 16-byte aligned; element j = v dim + c takes normal j % 4 of block ctr0 + j / 4 under
+ * `seed`. dim is any value >= 1. The noise pass writes out in tiles of EFL_DP_EMBED_NOISE_TILE elements
+ * and reads nothing for a tile none of whose rows is hit.
+ * efl_dp_embed_work_elems: doubles of `work` (one slot per microbatch and layer; clip_mode 1 only).
+ * efl_dp_embed_scratch_bytes: bytes of `scratch` (always needed, 16-byte aligned device memory: per layer
+ * the sorted ids, one combined row per entry and one range per tile of out). efl_dp_embed_sqnorm writes
+ * the layers' slots [slot0, slot0 + nlayers) of a shared work buffer (above). clip_mode, l2_norm_clip,
+ * mode, sigma, divisor, seed and scales are efl_dp_clip_sum's. `layers` is a HOST array; it travels to
+ * the kernels by value, 32 layers per launch (84 bytes each of the 4 KiB argument space): no allocation,
+ * no copy, no host synchronisation. out and scratch must not overlap the inputs. nlayers == 0 is a no-op.
+ * EFL_E_INVALID_ARGUMENT, before any HIP call, for: what efl_dp_dense_clip_sum refuses; V, dim or L < 1
+ * (V above 2^31 - 1); B L > 8,192; a null ids, d or out; an out that is not 16-byte aligned; a d_l_stride
+ * that is neither 0 nor at least dim; a d row stride below its width (L - 1) d_l_stride + dim; a null,
+ * misaligned or short scratch. */
+#define EFL_DP_EMBED_NOISE_TILE 4096
+typedef struct efl_dp_embed {
+  const int64_t* ids;                      /* [B, L] contiguous             */
+  const float* d;                          /* dLoss/d(output), rows of dim  */
+  int64_t d_row_stride, d_l_stride;        /* per example, per entry (0: a bag) */
+  float* out;                              /* [V, dim] contiguous           */
+  int64_t V;
+  int32_t dim, L;
+  float w;                                 /* weight of every entry         */
+  uint64_t ctr0;                           /* first Philox block of out     */
+} efl_dp_embed;
+int64_t efl_dp_embed_work_elems(int64_t nlayers, int64_t rows);
+int64_t efl_dp_embed_scratch_bytes(const efl_dp_embed* layers, int64_t nlayers, int64_t B);
+int efl_dp_embed_sqnorm(const efl_dp_embed* layers, int64_t nlayers, int64_t B, int64_t rows, double* work,
+                        int64_t slot0, int64_t slots, void* stream);
+int efl_dp_embed_clip_sum(const efl_dp_embed* layers, int64_t nlayers, int64_t B, int64_t rows, int clip_mode,
+                          float l2_norm_clip, int mode, float sigma, float divisor, uint64_t seed,
+                          float* scales, double* work, int64_t work_elems, void* scratch,
+                          int64_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

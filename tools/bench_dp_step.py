@@ -11,6 +11,15 @@
            (1024 -> 1024 -> 1024 -> 10) takes those instead. microbatch_gradients="factored" is timed
            beside the two (csrc/dpdense.hip for the Linear modules, csrc/dpconv.hip for dp_cnn's Conv2d
            modules), with each path's peak device memory over a step.
+           --model criteo_embed is the criteo example's shape with its embedding tables in: 21
+           EmbeddingBag(V_i, 8, mode="mean") tables of one hashed id each (V_i spread geometrically from 3 to
+           the example's largest, 2,000,000 rows), then 168 -> 64 -> 16 -> 2. Run it with --paths loop,factored:
+           "batched" cannot allocate its [256, V, 8] stacks (16 GB for the largest table alone). --loop-rounds
+           gives the slow path fewer rounds. The table sizes are this tool's own, not the example's list of
+           hash-bucket sizes. After the step it times efl_dp_embed_clip_sum with clip mode 0 on the largest
+           table, the WHOLE call: the 256 ids' sort (one launch) and the noise of 16,000,000 floats (one
+           launch), against efl_dp_noise over as many floats, HIP events around `--inner` calls, in alternating
+           rounds. The C ABI has no entry for the noise launch alone; a kernel trace splits the call.
   kernels  efl_dp_clip_sum alone at [256, 1 Mi] float32 (clip mode 1: the norm pass reads the stack
            once, the sum pass once more; clip mode 0: one read), HIP events around `--inner` calls,
            as a fraction of the 8 TB/s HBM peak: algorithmic bytes (reads of the stack + one write of
@@ -35,7 +44,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--inner", type=int, default=20)
 ap.add_argument("--batch", type=int, default=256)
-ap.add_argument("--model", choices=["dp_cnn", "criteo_mlp", "wide_mlp"], default="dp_cnn")
+ap.add_argument("--model", choices=["dp_cnn", "criteo_mlp", "wide_mlp", "criteo_embed"], default="dp_cnn")
+ap.add_argument("--loop-rounds", type=int, default=None, help='rounds of the "loop" path (default: --rounds)')
 ap.add_argument("--paths", default="loop,batched,factored",
                 help="the microbatch_gradients paths to time, the first the one the others are compared with")
 ap.add_argument("--no-kernels", action="store_true", help="skip the efl_dp_clip_sum kernel measurement")
@@ -65,7 +75,24 @@ model = nn.Sequential(nn.Conv2d(1, 16, 8, stride=2, padding=3), nn.ReLU(), nn.Ma
                       nn.Linear(512, 32), nn.ReLU(), nn.Linear(32, 10)).to(dev)
 x = torch.randn(args.batch, 1, 28, 28, device=dev)
 paths = tuple(args.paths.split(","))
-if args.model != "dp_cnn":
+
+TABLES = [round(3 * (2.0e6 / 3) ** (i / 20)) for i in range(21)]
+
+
+class CriteoEmbed(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.tables = nn.ModuleList(nn.EmbeddingBag(v, 8, mode="mean") for v in TABLES)
+        self.mlp = nn.Sequential(nn.Linear(8 * len(TABLES), 64), nn.ReLU(), nn.Linear(64, 16), nn.ReLU(), nn.Linear(16, 2))
+
+    def forward(self, ids):
+        return self.mlp(torch.cat([t(ids[:, i:i + 1]) for i, t in enumerate(self.tables)], 1))
+
+
+if args.model == "criteo_embed":
+    model = CriteoEmbed().to(dev)
+    x = torch.stack([torch.randint(0, v, (args.batch,), device=dev) for v in TABLES], 1)
+elif args.model != "dp_cnn":
     widths = (181, 64, 16, 2) if args.model == "criteo_mlp" else (1024, 1024, 1024, 10)
     model = nn.Sequential(*[m for i, o in zip(widths, widths[1:]) for m in (nn.Linear(i, o), nn.ReLU())][:-1]).to(dev)
     x = torch.randn(args.batch, widths[0], device=dev)
@@ -73,13 +100,17 @@ if args.model != "dp_cnn":
 import copy  # noqa: E402
 models = {p: copy.deepcopy(model) if p == "factored" else model for p in paths}
 params = list(model.parameters())
-y = torch.randint(0, model[-1].out_features, (args.batch,), device=dev)
+y = torch.randint(0, [m for m in model.modules() if isinstance(m, nn.Linear)][-1].out_features, (args.batch,), device=dev)
+
+
+def of_kind(path, *kinds):
+    return [m for m in models[path].modules() if isinstance(m, kinds)] if path == "factored" else None
+
+
 opts = {p: efl.privacy.DPGradientDescentGaussianOptimizer(list(models[p].parameters()), noise_multiplier=1.0,
                                                           l2_norm_clip=1.0, learning_rate=0.25, microbatch_gradients=p,
-                                                          dense_layers=[m for m in models[p] if isinstance(m, nn.Linear)]
-                                                          if p == "factored" else None,
-                                                          conv_layers=[m for m in models[p] if isinstance(m, nn.Conv2d)]
-                                                          if p == "factored" else None)
+                                                          dense_layers=of_kind(p, nn.Linear), conv_layers=of_kind(p, nn.Conv2d),
+                                                          embedding_layers=of_kind(p, nn.EmbeddingBag))
         for p in paths}
 
 
@@ -108,18 +139,54 @@ for p in opts:
     step(p)
     peak[p] = torch.cuda.max_memory_allocated()
 times = {p: [] for p in opts}
-for _ in range(args.rounds):
+for k in range(args.rounds):
     for p in opts:
-        times[p].append(step(p)[0])
+        if p != "loop" or args.loop_rounds is None or k < args.loop_rounds:
+            times[p].append(step(p)[0])
 med = {p: float(np.median(t)) for p, t in times.items()}
 emit({"bench": "dp_step_compute_gradients", "model": args.model, "batch": args.batch, "microbatches": args.batch,
-      "variables": len(params), "floats": sum(p.numel() for p in params), "rounds": args.rounds,
+      "variables": len(params), "floats": sum(p.numel() for p in params), "rounds": args.rounds, **({"loop_rounds": len(times["loop"])} if args.loop_rounds and "loop" in times else {}),
       "ms_per_step": {p: round(v, 3) for p, v in med.items()},
       "ms_min_max": {p: [round(min(t), 3), round(max(t), 3)] for p, t in times.items()},
       "peak_bytes": peak,
       **({"loop_over_batched": round(med["loop"] / med["batched"], 2)} if "loop" in med and "batched" in med else {}),
       **({"batched_over_factored": round(med["batched"] / med["factored"], 2)} if "batched" in med and "factored" in med else {}),
       "max_rel_diff": diff})
+if args.model == "criteo_embed":
+    # ---- the dense pass over the largest table against efl_dp_noise over as many floats ---------
+    lib, V, dim, B = efl.lib.raw(), max(TABLES), 8, args.batch
+    stream = torch.cuda.current_stream()
+    ids, d = torch.randint(0, V, (B, 1), device=dev), torch.randn(B, dim, device=dev)
+    out, zeros = torch.empty(V, dim, device=dev), torch.zeros(V * dim, device=dev)
+    arr = (efl.lib.DpEmbed * 1)()
+    L = arr[0]
+    L.ids, L.d, L.out, L.V, L.dim, L.L, L.w, L.d_row_stride, L.d_l_stride = ids.data_ptr(), d.data_ptr(), out.data_ptr(), V, dim, 1, 1.0, dim, 0
+    nbytes = lib.efl_dp_embed_scratch_bytes(arr, 1, B)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    calls = {"embed_clip_sum": lambda: efl.lib.check(lib.efl_dp_embed_clip_sum(
+                 arr, 1, B, B, 0, 0.0, 1, 1.0, float(B), 7, None, None, 0, scratch.data_ptr(), nbytes, stream.cuda_stream)),
+             "dp_noise": lambda: efl.lib.check(lib.efl_dp_noise(zeros.data_ptr(), zeros.data_ptr(), V * dim, 1, 0.0, 1.0, 7, 0,
+                                                                stream.cuda_stream))}
+    kt = {k: [] for k in calls}
+    for k in range(args.rounds + 1):                # the first round warms up
+        for name, fn in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(args.inner):
+                fn()
+            e1.record(stream)
+            e1.synchronize()
+            if k:
+                kt[name].append(e0.elapsed_time(e1) / args.inner)
+    med = {k: float(np.median(t)) for k, t in kt.items()}
+    emit({"bench": "dp_embed_clip_sum_call", "measures": "efl_dp_embed_clip_sum, clip mode 0: the group launch and the noise "
+          "launch together (the noise launch alone is not timed here); hbm_frac: bytes written by the call / its time",
+          "table": [V, dim], "entries": B, "calls_per_round": args.inner, "rounds": args.rounds,
+          "ms_per_call": {k: round(v, 4) for k, v in med.items()},
+          "ms_min_max": {k: [round(min(t), 4), round(max(t), 4)] for k, t in kt.items()},
+          "hbm_frac": {"embed_clip_sum": round(4 * V * dim / (med["embed_clip_sum"] * 1e-3) / HBM_PEAK, 4),
+                       "dp_noise": round(8 * V * dim / (med["dp_noise"] * 1e-3) / HBM_PEAK, 4)},
+          "embed_median_no_slower_than_dp_noise_slowest": med["embed_clip_sum"] <= max(kt["dp_noise"])})
 if args.no_kernels:
     sys.exit(0)
 
