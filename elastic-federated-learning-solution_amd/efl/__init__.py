@@ -12,6 +12,7 @@ Public names mirror efls-train/python/efl (exporter registry, efl/__init__.py:47
   efl.psi.IdStore (the signed-ID store: a device hash table with the dict's semantics),
   efl.psi.{EcdhJoinServer, EcdhJoinClient} (the ECDH join on top of it, without the transport)
   efl.psi.{RsaJoinServer, RsaJoinClient} (the RSA join), efl.psi.rsa_cipher.{decimal_rows, oneway_rows}
+  efl.metrics.{auc, gauc, Auc, Gauc} (streaming AUC with tf.metrics.auc's thresholds; grouped AUC)
 The kernels live in libefl_hip.so (C ABI: include/efl_hip.h); there is no CPU fallback.
 """
 from efl import exporter
@@ -26,6 +27,7 @@ from efl.privacy import paillier_layer
 from efl.privacy import secret_sharing
 from efl.privacy.hex_tensor import HexTensor
 from efl import psi
+from efl import metrics
 from efl.framework import communicator
 from efl.framework import encrypt_hook
 from efl.framework.communicator import Communicator, TensorHook

@@ -75,6 +75,12 @@ _SIGS = {
     "efl_dp_embed_sqnorm": ([_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp], _i32),
     "efl_dp_embed_clip_sum": ([_vp, _i64, _i64, _i64, _i32, ctypes.c_float, _i32, ctypes.c_float, ctypes.c_float,
                                ctypes.c_uint64, _vp, _vp, _i64, _vp, _i64, _vp], _i32),
+    # efl.metrics: the thresholded AUC's histogram and value, and the grouped AUC (csrc/auc.hip)
+    "efl_auc_work_elems": ([_i64, _i32], _i64),
+    "efl_auc_update": ([_vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp, _i64, _vp], _i32),
+    "efl_auc_value": ([_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp], _i32),
+    "efl_gauc_scratch_bytes": ([_i64], _i64),
+    "efl_gauc_update": ([_vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp], _i32),
     # RSA blind-signature PSI (efl.psi; include/efl_hip.h efl_rsa_*): contexts and info structs as void*
     "efl_rsa_ctx_create": ([_vp], _i32),
     "efl_rsa_ctx_destroy": ([_vp], _i32),
@@ -166,10 +172,13 @@ class DpEmbed(ctypes.Structure):
 
 DP_EMBED_NOISE_TILE = 4096      # EFL_DP_EMBED_NOISE_TILE: elements of a table per workgroup of the noise pass
 DP_EMBED_MAX_ENTRIES = 8192     # B L of one layer: its sort keys fill the 64 KiB of LDS
+AUC_TILE = 2048                 # EFL_AUC_TILE: elements per tile of efl_auc_update and of efl_gauc_update's sort
+GAUC_MAX_N = 1 << 22            # EFL_GAUC_MAX_N: elements of one efl_gauc_update
 
 
 # TensorFlow DataType numbers (types.proto), as used by the C ABI and the wire format.
 DT_FLOAT, DT_DOUBLE, DT_INT32, DT_INT16, DT_INT8, DT_STRING, DT_INT64 = 1, 2, 3, 5, 6, 7, 9
+DT_UINT8, DT_BOOL = 4, 10       # label types of efl.metrics only
 _TORCH_TO_DT = {torch.float32: DT_FLOAT, torch.float64: DT_DOUBLE, torch.int32: DT_INT32,
                 torch.int16: DT_INT16, torch.int8: DT_INT8, torch.int64: DT_INT64}
 _DT_TO_TORCH = {v: k for k, v in _TORCH_TO_DT.items()}

@@ -985,6 +985,56 @@ int efl_dp_embed_clip_sum(const efl_dp_embed* layers, int64_t nlayers, int64_t B
                           float* scales, double* work, int64_t work_elems, void* scratch,
                           int64_t scratch_bytes, void* stream);
 
+/* efl.metrics.auc: tf.metrics.auc of TF 1.15 as a running histogram (csrc/auc.hip). With
+ * T = num_thresholds in [2, 4096]: thr[0] = -1e-7, thr[T - 1] = 1 + 1e-7, thr[i] = i / (T - 1), each formed
+ * in double and rounded once to float. An element is predicted positive at threshold t iff
+ * predictions[i] > thr[t], compared in float; its label is positive iff it is non-zero. Its bucket is
+ * k = #{t : p > thr[t]} in [0, T] (a NaN: 0). The state is double [2][T + 1], the summed weight per
+ * (label, bucket); the caller zeroes it to reset the metric. tp[t] = sum over k > t of state[1][k],
+ * fn[t] = sum over k <= t; fp and tn the same over state[0].
+ * efl_auc_update adds n elements to the state: one launch of per-workgroup partial histograms into `work`
+ * (efl_auc_work_elems(n, T) doubles), one that adds them to the state in workgroup order. label_dtype is
+ * a TensorFlow DataType number: DT_FLOAT 1, DT_INT32 3, DT_UINT8 4, DT_INT64 9, DT_BOOL 10 (a byte).
+ * weights == NULL: every weight is 1 and the counts are integers, exact while the totals stay below 2^53.
+ * With weights the sums are in double, a workgroup's tiles in element order, without atomics: the same
+ * inputs give the same bytes, and an entry differs from the exact sum by at most n 2^-53 sum |w|.
+ * predictions, weights and labels are 16-byte aligned (byte labels: 4). n in [0, 2^31 - 1]; n == 0 is a
+ * no-op.
+ * efl_auc_value: one launch, nothing synchronises. confusion [4][T] takes tp, fp, tn, fn; with
+ * eps = 1e-6, rec = (tp + eps) / (tp + fn + eps), fpr = fp / (fp + tn + eps),
+ * prec = (tp + eps) / (tp + fp + eps). curve 0 (ROC): x = fpr, y = rec; 1 (PR): x = rec, y = prec.
+ * summation_method 0 (trapezoidal): sum of (x[t] - x[t + 1]) (y[t] + y[t + 1]) / 2; 2 (minoring) and
+ * 3 (majoring): the smaller and the larger y for their mean; 1 (careful_interpolation): with PR TF's
+ * interpolate_pr_auc, with ROC the trapezoid. All of it in double: *value64, and *value = (float) of it.
+ * confusion must not overlap the state.
+ * EFL_E_INVALID_ARGUMENT, before any HIP call, for: T outside [2, 4096]; n outside [0, 2^31 - 1]; an
+ * unknown label_dtype, curve or summation_method; a null or misaligned buffer; a short work buffer. */
+#define EFL_AUC_TILE 2048
+int64_t efl_auc_work_elems(int64_t n, int num_thresholds);
+int efl_auc_update(const float* predictions, const void* labels, int label_dtype, const float* weights, int64_t n,
+                   int num_thresholds, double* state, double* work, int64_t work_elems, void* stream);
+int efl_auc_value(const double* state, int num_thresholds, int curve, int summation_method, float* value,
+                  double* value64, double* confusion, void* stream);
+
+/* efl.metrics.gauc: the grouped AUC (csrc/auc.hip). The reference's gauc calls an op it never defines, so
+ * the definition is this one. A group is all elements of the call with the same indicator, wherever they
+ * lie. A group with P positives (label non-zero) and N negatives, P N > 0, has AUC_g = U / (P N), U
+ * counting 1 for each (positive, negative) pair whose positive has the greater prediction and 1/2 for
+ * each pair with equal predictions; -0.0 equals +0.0 and every NaN is one value above every number.
+ * Groups with P N = 0 are left out. The call's total = sum of n_g AUC_g and count = sum of n_g over the
+ * groups kept (n_g = P + N) go to call_out[0..1] (may be NULL) and are added to state[0..1]; *value64 =
+ * state[0] / state[1] (0 when the count is 0) and *value = (float) of it.
+ * 2U is an exact int64; AUC_g is one double division per group; the sums go through one slot per
+ * workgroup in slot order: the same inputs give the same bytes. n is at most EFL_GAUC_MAX_N per call;
+ * scratch is 16-byte aligned device memory of efl_gauc_scratch_bytes(n) bytes. label_dtype as above.
+ * EFL_E_INVALID_ARGUMENT, before any HIP call, for: n outside [0, 2^22]; an unknown label_dtype; a null
+ * or misaligned buffer; a short scratch. */
+#define EFL_GAUC_MAX_N 4194304
+int64_t efl_gauc_scratch_bytes(int64_t n);
+int efl_gauc_update(const float* predictions, const void* labels, int label_dtype, const int64_t* indicators,
+                    int64_t n, double* state, double* call_out, float* value, double* value64, void* scratch,
+                    int64_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
