@@ -75,6 +75,12 @@ _SIGS = {
     "efl_dp_embed_sqnorm": ([_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp], _i32),
     "efl_dp_embed_clip_sum": ([_vp, _i64, _i64, _i64, _i32, ctypes.c_float, _i32, ctypes.c_float, ctypes.c_float,
                                ctypes.c_uint64, _vp, _vp, _i64, _vp, _i64, _vp], _i32),
+    # the same step for Linear layers over sequences [B, T, in]: layers is a host array of DpSeq
+    "efl_dp_seq_work_elems": ([_vp, _i64, _i64, _i64], _i64),
+    "efl_dp_seq_partial_elems": ([_vp, _i64, _i64, _i64], _i64),
+    "efl_dp_seq_sqnorm": ([_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp], _i32),
+    "efl_dp_seq_clip_sum": ([_vp, _i64, _i64, _i64, _i32, ctypes.c_float, _i32, ctypes.c_float, ctypes.c_float,
+                             ctypes.c_uint64, _vp, _vp, _i64, _vp, _i64, _vp], _i32),
     # efl.metrics: the thresholded AUC's histogram and value, and the grouped AUC (csrc/auc.hip)
     "efl_auc_work_elems": ([_i64, _i32], _i64),
     "efl_auc_update": ([_vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp, _i64, _vp], _i32),
@@ -170,6 +176,16 @@ class DpEmbed(ctypes.Structure):
                 ("dim", ctypes.c_int32), ("L", ctypes.c_int32), ("w", ctypes.c_float), ("ctr0", ctypes.c_uint64)]
 
 
+class DpSeq(ctypes.Structure):
+    """efl_dp_seq (include/efl_hip.h): one Linear layer over a sequence of efl_dp_seq_clip_sum, its input
+    x [B, T, in] and the gradient d [B, T, out] of the summed loss by its output as rows of the flattened
+    [B T, .] matrices, and its [out, in] / [out] outputs."""
+    _fields_ = [("x", _vp), ("x_row_stride", _i64), ("d", _vp), ("d_row_stride", _i64), ("w_out", _vp),
+                ("b_out", _vp), ("T", _i64), ("in_", _i64), ("out", _i64), ("ctr0_w", ctypes.c_uint64),
+                ("ctr0_b", ctypes.c_uint64)]
+
+
+DP_SEQ_MAX_ROWS = 8192          # r T of one layer: (example, position) rows per microbatch of efl_dp_seq_clip_sum
 DP_EMBED_NOISE_TILE = 4096      # EFL_DP_EMBED_NOISE_TILE: elements of a table per workgroup of the noise pass
 DP_EMBED_MAX_ENTRIES = 8192     # B L of one layer: its sort keys fill the 64 KiB of LDS
 AUC_TILE = 2048                 # EFL_AUC_TILE: elements per tile of efl_auc_update and of efl_gauc_update's sort

@@ -42,7 +42,12 @@ input) tables given as `embedding_layers=` are the third family (csrc/dpembed.hi
 `dp_embed_clip_sum_noise`): a microbatch's gradient of a table is zero but for the rows its ids name, so the
 norm and the clipped sum come from a sort of the step's at most 8,192 (id, entry) keys per table and the
 entries' rows of d, and the only dense pass is the noise, one write of the table and no read. A recommender
-of tables and an MLP runs under one norm. A model with any other variable is out of its scope.
+of tables and an MLP runs under one norm. A Linear of `dense_layers=` applied at every position of a sequence
+(input [B, *, in]: T positions per example) is the fourth (csrc/dpseq.hip's efl_dp_seq_clip_sum): a microbatch
+of r examples has P = r T rows (at most 8,192), its norm is sum Gd (Gx + 1) over the [P, P] Grams of the rows
+of X and of D, formed in 64 x 64 blocks on the fp64 matrix cores and never stored, and its sum is the GEMM
+D^T diag(s) X over all B T rows, split over groups of microbatches. A model with any other variable is out of
+its scope.
 
 Torch mapping. TF optimisers get their variables at minimize time; torch ones at construction.
 These classes take either: `params` (as `params=`, or first positional with the DP arguments as
@@ -105,6 +110,7 @@ MICROBATCH_GRADIENTS = ("loop", "batched")       # for any model and any query
 DENSE_MICROBATCH_GRADIENTS = ("factored",)        # for models of registered Linear layers (dense_layers=)
 MAX_ROWS_PER_MICROBATCH = 16                      # efl_dp_dense_clip_sum's limit on batch rows per microbatch
 MAX_EMBEDDING_ENTRIES = lib.DP_EMBED_MAX_ENTRIES  # efl_dp_embed_clip_sum's limit on looked-up ids per table and step
+MAX_SEQUENCE_ROWS = lib.DP_SEQ_MAX_ROWS           # efl_dp_seq_clip_sum's limit on (example, position) rows per microbatch
 _microbatch_gradients = "loop"
 
 
@@ -247,23 +253,92 @@ def _dense_clip_sum(layers, rows, l2_norm_clip, mode, sigma, divisor, seed, ctrs
 
 
 def _check_dense_layers(layers, rows, who):
+    """[(x, d, has_bias)] with detached tensors: x [B, in] and d [B, out] as they are (csrc/dpdense.hip's
+    layers), x [B, *, in] and d [B, *, out] flattened to [B, T, .] (csrc/dpseq.hip's)."""
     layers = [(lib.as_tensor(x).detach(), lib.as_tensor(d).detach(), bool(has_bias)) for x, d, has_bias in layers]
     dev, B = layers[0][0].device, layers[0][0].shape[0] if layers[0][0].dim() else 0
-    for x, d, _ in layers:
+    for k, (x, d, has_bias) in enumerate(layers):
         if x.dtype != torch.float32 or d.dtype != torch.float32:
             raise errors.InvalidArgumentError(f"{who}: x and d must be float32, got {x.dtype} and {d.dtype}")
         if x.device != dev or d.device != dev or dev.type != "cuda":
             raise errors.InvalidArgumentError(f"{who}: every x and d lies on one ROCm device")
-        if x.dim() != 2 or d.dim() != 2 or x.shape[0] != B or d.shape[0] != B or 0 in x.shape or 0 in d.shape:
+        if x.dim() < 2 or d.dim() < 2 or x.shape[0] != B or d.shape[0] != B or 0 in x.shape or 0 in d.shape:
             raise errors.InvalidArgumentError(
                 f"{who}: a layer takes x [B, in] and d [B, out] with B = {B}, got {tuple(x.shape)} and {tuple(d.shape)}")
+        if x.shape[1:-1] != d.shape[1:-1]:
+            raise errors.InvalidArgumentError(
+                f"{who}: a layer over a sequence takes x [B, *, in] and d [B, *, out] with equal middle dimensions, "
+                f"got {tuple(x.shape)} and {tuple(d.shape)}")
+        if x.dim() > 2:
+            layers[k] = (x.reshape(B, -1, x.shape[-1]), d.reshape(B, -1, d.shape[-1]), has_bias)
     rows = int(rows)
     if rows < 1 or B % rows:
         raise errors.InvalidArgumentError(f"{who}: {rows} microbatches do not divide the batch of {B}")
     if B // rows > MAX_ROWS_PER_MICROBATCH:
         raise errors.InvalidArgumentError(f"{who}: {B // rows} examples per microbatch, at most "
                                           f"{MAX_ROWS_PER_MICROBATCH} (r > {MAX_ROWS_PER_MICROBATCH})")
+    for x, _, _ in layers:
+        if x.dim() == 3 and B // rows * x.shape[1] > MAX_SEQUENCE_ROWS:
+            raise errors.InvalidArgumentError(
+                f"{who}: {B // rows} examples of {x.shape[1]} positions per microbatch, at most {MAX_SEQUENCE_ROWS} "
+                f"rows (r T > {MAX_SEQUENCE_ROWS})")
     return layers, rows
+
+
+def _seq_table(layers, ctrs):
+    """The DpSeq table of checked sequence layers [(x [B, T, in], d [B, T, out], has_bias)] with freshly
+    carved outputs: (table, [(w_grad, b_grad | None)], tensors to keep alive). A tensor whose positions are
+    contiguous rows at least a width apart is taken as it lies (a padded row stride included)."""
+    dev, like = layers[0][0].device, []
+    for x, d, has_bias in layers:
+        like.append(torch.empty(d.shape[2], x.shape[2], device="meta"))
+        if has_bias:
+            like.append(torch.empty(d.shape[2], device="meta"))
+    flat = iter(lib._carve(like, torch.float32, dev))
+    arr, outs, keep = (lib.DpSeq * len(layers))(), [], []
+
+    def rows_of(t):     # the flattened [B T, width] rows and their stride
+        B, T, width = t.shape
+        s = t.stride(1) if T > 1 else t.stride(0) if B > 1 else width
+        if t.stride(2) != 1 or s < width or (B > 1 and T > 1 and t.stride(0) != T * s) or t.data_ptr() % 4:
+            t, s = t.contiguous(), width
+        return t, s
+
+    for rec, (x, d, has_bias), (cw, cb) in zip(arr, layers, ctrs):
+        (x, xs), (d, ds) = rows_of(x), rows_of(d)
+        keep += [x, d]
+        w, b = next(flat), next(flat) if has_bias else None
+        rec.x, rec.x_row_stride, rec.d, rec.d_row_stride = x.data_ptr(), xs, d.data_ptr(), ds
+        rec.w_out, rec.b_out, rec.T, rec.in_, rec.out = w.data_ptr(), None if b is None else b.data_ptr(), x.shape[1], x.shape[2], d.shape[2]
+        rec.ctr0_w, rec.ctr0_b = cw, cb
+        outs.append((w, b))
+    return arr, outs, keep
+
+
+def _seq_clip_sum(layers, rows, l2_norm_clip, mode, sigma, divisor, seed, ctrs, scales, table=None):
+    """efl_dp_seq_clip_sum over checked sequence layers; ctrs: per layer the first Philox block of (weight,
+    bias); table: their _seq_table when the caller has made it. Returns ([(w_grad, b_grad | None)],
+    scales | None)."""
+    dev, B, raw = layers[0][0].device, layers[0][0].shape[0], lib.raw()
+    arr, outs, keep = table or _seq_table(layers, ctrs)
+    clip_mode = 2 if scales is not None else 0 if l2_norm_clip is None else 1
+    work, work_elems = None, 0
+    if clip_mode == 2:
+        scales = lib.as_tensor(scales).detach().to(dev, torch.float32).contiguous()
+        if scales.shape != (rows,):
+            raise errors.InvalidArgumentError(f"dp_dense_clip_sum_noise: scales must be [{rows}]")
+    elif clip_mode == 1:
+        work_elems = _elems(raw.efl_dp_seq_work_elems(arr, len(layers), B, rows))
+        work = torch.empty(max(work_elems, 1), dtype=torch.float64, device=dev)
+        scales = torch.empty(rows, dtype=torch.float32, device=dev)
+    pe = _elems(raw.efl_dp_seq_partial_elems(arr, len(layers), B, rows))
+    partials = torch.empty(max(pe, 4), dtype=torch.float32, device=dev)
+    lib.check(raw.efl_dp_seq_clip_sum(arr, len(layers), B, rows, clip_mode, float(l2_norm_clip or 0.0), int(mode),
+                                      float(sigma), float(divisor), seed,
+                                      None if scales is None else scales.data_ptr(),
+                                      None if work is None else work.data_ptr(), work_elems, partials.data_ptr(), pe,
+                                      lib.stream_handle(dev)))
+    return outs, scales
 
 
 @exporter.export("privacy.dp_dense_clip_sum_noise")
@@ -279,16 +354,20 @@ def dp_dense_clip_sum_noise(layers, rows: int, l2_norm_clip, mode: int, sigma: f
     the process's) one take(numel) per variable, weight then bias, in layer order.
     scale_i: 1 with l2_norm_clip None and no `scales`; `scales` ([rows] float32) when given; else
     clip * min(1 / ||g_i||, 1 / clip), g_i microbatch i's gradient of all the layers' variables, its
-    norm from the layers' Gram matrices in double. return_scales: also return the [rows] scales."""
+    norm from the layers' Gram matrices in double. return_scales: also return the [rows] scales.
+    A layer applied at every position of a sequence gives x [B, *, in] and d [B, *, out] with equal middle
+    dimensions (T positions in all, at most 8,192 / (B / rows)): it takes efl_dp_seq_clip_sum
+    (csrc/dpseq.hip), its norm from the [r T, r T] Grams on the fp64 matrix cores, under the same shared
+    norm and at the same stream positions."""
     layers = list(layers)
     if not layers:
         return ([], None) if return_scales else []
     layers, rows = _check_dense_layers(layers, rows, "dp_dense_clip_sum_noise")
     ctrs, seed = [], None
     for x, d, has_bias in layers:
-        seed, cw = (stream or _stream).take(d.shape[1] * x.shape[1])
-        ctrs.append((cw, (stream or _stream).take(d.shape[1])[1] if has_bias else 0))
-    outs, scales = _dense_clip_sum(layers, rows, l2_norm_clip, mode, sigma, divisor, seed, ctrs, scales)
+        seed, cw = (stream or _stream).take(d.shape[-1] * x.shape[-1])
+        ctrs.append((cw, (stream or _stream).take(d.shape[-1])[1] if has_bias else 0))
+    outs, _, _, scales = _factored_clip_sum(layers, [], rows, l2_norm_clip, mode, sigma, divisor, seed, ctrs, [], scales)
     if return_scales:
         return outs, torch.ones(rows, device=layers[0][0].device) if scales is None else scales
     return outs
@@ -538,26 +617,41 @@ def _factored_clip_sum(dense, conv, rows, l2_norm_clip, mode, sigma, divisor, se
     """Checked dense, conv and embedding layers under ONE norm: (dense outs, conv outs, embedding outs,
     scales | None). With more than one family and no given scales, all write their norm slots into one work
     buffer [rows, slots] (dense, then conv, then embedding), efl_dp_scales makes the scales, and every sum
-    runs with them (clip_mode 2)."""
-    dtab = ctab = etab = None
-    if (bool(dense) + bool(conv) + bool(embed)) > 1 and scales is None and l2_norm_clip is not None:
-        first = dense[0][0] if dense else conv[0][0]
+    runs with them (clip_mode 2). The dense layers over sequences (x [B, T, in]) are a family of their own
+    (csrc/dpseq.hip), their slots after the 2-D dense layers'; their outputs come back in `dense`'s order."""
+    seq_at = [k for k, (x, _, _) in enumerate(dense) if x.dim() == 3]
+    seq, sctrs = [dense[k] for k in seq_at], [dctrs[k] for k in seq_at]
+    dense_at = [k for k in range(len(dense)) if k not in seq_at]
+    dense, dctrs = [dense[k] for k in dense_at], [dctrs[k] for k in dense_at]
+    dtab = stab = ctab = etab = None
+    if (bool(dense) + bool(seq) + bool(conv) + bool(embed)) > 1 and scales is None and l2_norm_clip is not None:
+        first = dense[0][0] if dense else seq[0][0] if seq else conv[0][0]
         dev, B, raw, h = first.device, first.shape[0], lib.raw(), lib.stream_handle(first.device)
         dtab, ctab, etab = dense and _dense_table(dense, dctrs), conv and _conv_table(conv, cctrs), embed and _embed_table(embed, ectrs)
+        stab = seq and _seq_table(seq, sctrs)
+        ns = _elems(raw.efl_dp_seq_work_elems(stab[0], len(seq), B, rows)) // rows if seq else 0
         nc = _elems(raw.efl_dp_conv_work_elems(ctab[0], len(conv), rows)) // rows if conv else 0
-        slots = len(dense) + nc + len(embed)
+        slots = len(dense) + ns + nc + len(embed)
         work = torch.empty(rows * slots, dtype=torch.float64, device=dev)
         scales = torch.empty(rows, dtype=torch.float32, device=dev)
         if dense:
             lib.check(raw.efl_dp_dense_sqnorm(dtab[0], len(dense), B, rows, work.data_ptr(), 0, slots, h))
+        if seq:
+            lib.check(raw.efl_dp_seq_sqnorm(stab[0], len(seq), B, rows, work.data_ptr(), len(dense), slots, h))
         if conv:
-            lib.check(raw.efl_dp_conv_sqnorm(ctab[0], len(conv), B, rows, work.data_ptr(), len(dense), slots, h))
+            lib.check(raw.efl_dp_conv_sqnorm(ctab[0], len(conv), B, rows, work.data_ptr(), len(dense) + ns, slots, h))
         if embed:
-            lib.check(raw.efl_dp_embed_sqnorm(etab[0], len(embed), B, rows, work.data_ptr(), len(dense) + nc, slots, h))
+            lib.check(raw.efl_dp_embed_sqnorm(etab[0], len(embed), B, rows, work.data_ptr(), len(dense) + ns + nc, slots, h))
         lib.check(raw.efl_dp_scales(work.data_ptr(), slots, rows, float(l2_norm_clip), scales.data_ptr(), h))
     douts = couts = eouts = []
     if dense:                               # one family alone takes its own norm pass (clip_mode 1)
         douts, scales = _dense_clip_sum(dense, rows, l2_norm_clip, mode, sigma, divisor, seed, dctrs, scales, dtab or None)
+    if seq:
+        souts, scales = _seq_clip_sum(seq, rows, l2_norm_clip, mode, sigma, divisor, seed, sctrs, scales, stab or None)
+        merged = [None] * (len(dense_at) + len(seq_at))
+        for k, o in zip(dense_at + seq_at, [*douts, *souts]):
+            merged[k] = o
+        douts = merged
     if conv:
         couts, scales = _conv_clip_sum(conv, rows, l2_norm_clip, mode, sigma, divisor, seed, cctrs, scales, ctab or None)
     if embed:
@@ -590,7 +684,7 @@ def dp_factored_clip_sum_noise(dense_layers, conv_layers, rows: int, l2_norm_cli
     if any(t.shape[0] != firsts[0].shape[0] or t.device != firsts[0].device for t in firsts):
         raise errors.InvalidArgumentError(f"{who}: the dense, conv and embedding layers take one batch on one device")
     st = stream or _stream
-    seed, dctrs = _take_layers([(d.shape[1] * x.shape[1], d.shape[1] if b else 0) for x, d, b in dense], st)
+    seed, dctrs = _take_layers([(d.shape[-1] * x.shape[-1], d.shape[-1] if b else 0) for x, d, b in dense], st)
     seed_c, cctrs = _take_layers(_conv_numels(conv), st)
     seed_e, ectrs = _take_layers([(V * d.shape[-1], 0) for _, d, V, _ in embed], st)
     seed = next(v for v in (seed, seed_c, seed_e) if v is not None)
@@ -949,10 +1043,10 @@ def make_optimizer_class(cls):
                         raise errors.InvalidArgumentError(
                             f"{who}: {layer} takes [B] or [B, L] ids with B = {batch} per-example losses and gives "
                             f"float32, got {tuple(x.shape)} and {out.dtype}")
-                elif (x.dim() != (4 if is_conv else 2) or x.shape[0] != batch or x.dtype != torch.float32
+                elif ((x.dim() != 4 if is_conv else x.dim() < 2) or x.shape[0] != batch or x.dtype != torch.float32
                         or out.dtype != torch.float32):
                     raise errors.InvalidArgumentError(
-                        f"{who}: {layer} takes a float32 {'[B, Cin, H, W]' if is_conv else '[B, in]'} input with "
+                        f"{who}: {layer} takes a float32 {'[B, Cin, H, W]' if is_conv else '[B, in] or [B, *, in]'} input with "
                         f"B = {batch} per-example losses, got {x.dtype} {tuple(x.shape)}")
                 layers.append((layer, wi, bi, x, out))
             go = torch.ones_like(loss) if grad_loss is None else grad_loss.reshape(loss.shape)

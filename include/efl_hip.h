@@ -985,6 +985,57 @@ int efl_dp_embed_clip_sum(const efl_dp_embed* layers, int64_t nlayers, int64_t B
                           float* scales, double* work, int64_t work_elems, void* scratch,
                           int64_t scratch_bytes, void* stream);
 
+/* The same step for Linear layers applied at every position of a sequence WITHOUT the stacked gradients
+ * (csrc/dpseq.hip). A layer gives its input x [B, T, in] and d [B, T, out], the gradient of the summed loss
+ * with respect to its output, both channel-minor: row k = b T + t of the flattened [B T, .] matrices at
+ * x + k x_row_stride and d + k d_row_stride. Microbatch i is the P = r T consecutive rows from i P,
+ * r = B / rows, 1 <= r <= 16, P <= 8,192. Its weight gradient is G_i = D_i^T X_i [out, in] and its bias
+ * gradient g_i = sum_p d_p; with the Grams Gx = X_i X_i^T and Gd = D_i D_i^T [P, P]
+ *   S_i = sum over layers of sum_{p, p'} Gd[p, p'] (Gx[p, p'] + beta),   beta = 1 with a bias, 0 without,
+ * which is ||G_i||_F^2 + ||g_i||^2: P^2 (in + out) products, fewer than the P in out of forming G_i while
+ * P < 2 in out / (in + out), and taken for every P.
+ * Rounding contract.
+ *   Scales: the Grams in 64 x 64 blocks of position tiles I <= J on v_mfma_f64_16x16x4_f64 over exactly
+ *   widened fp32 operands, never stored; a block's sum of Gd (Gx + beta) in double, an off-diagonal block
+ *   doubled, one slot per (microbatch, block), no atomics: the same bytes on every run. scale = (float)
+ *   (clip * min(1 / sqrt(S_i), 1 / clip)) rounded once, S_i the slots added in a fixed order; S_i = 0 gives
+ *   1 and an infinite S_i gives 0.
+ *   Sum: w_out [out, in] = noise(D^T diag(s_{k / P}) X) / divisor and b_out [out] = noise(sum_k s_{k / P} d_k)
+ *   / divisor, K = B T: s d rounded once, then fp32 accumulation on v_mfma_f32_32x32x2_f32 in a fixed order
+ *   within a split, the splits added in order, then efl_dp_noise's noise and division (through
+ *   efl_dp_clip_sum, clip_mode 0, over the partials). The reduction is split into min(rows, 16) groups of
+ *   ceil(rows / min(rows, 16)) consecutive microbatches (the last group ragged, empty groups dropped), a
+ *   function of `rows` alone: the same bytes on any device. Per element
+ *   |got - exact| <= (B T + splits + 3) 2^-24 (sum_k |s d x| + |noise|) / |divisor|   (the bias: sum |s d|).
+ * w_out and b_out (NULL: no bias, beta = 0) are 16-byte aligned; element j of each takes normal j % 4 of
+ * block ctr0_w / ctr0_b + j / 4 under `seed`.
+ * efl_dp_seq_work_elems: doubles of `work` (rows x the layers' tile pairs, n (n + 1) / 2 per layer with
+ * n = ceil(P / 64); clip_mode 1 only); it takes B because P depends on it. efl_dp_seq_partial_elems: floats
+ * of `partials` (always needed, 16-byte aligned). efl_dp_seq_sqnorm writes the layers' slots
+ * [slot0, slot0 + efl_dp_seq_work_elems / rows) of a shared work buffer (above). clip_mode, l2_norm_clip,
+ * mode, sigma, divisor, seed and scales are efl_dp_dense_clip_sum's. `layers` is a HOST array; it travels
+ * to the kernels by value, 24 layers per launch: no device allocation, no copy, stream-ordered. The outputs
+ * and the scratch must not overlap the inputs. nlayers == 0 is a no-op.
+ * EFL_E_INVALID_ARGUMENT, before any HIP call, for: what efl_dp_dense_clip_sum refuses; T < 1; B / rows > 16;
+ * r T > 8,192; a w_out or b_out that is not 16-byte aligned; a null, misaligned or short work (clip_mode 1)
+ * or partials. */
+typedef struct efl_dp_seq {
+  const float* x;  int64_t x_row_stride;   /* [B, T, in]  layer input, rows of the flattened [B T, in] */
+  const float* d;  int64_t d_row_stride;   /* [B, T, out] dLoss/d(output)   */
+  float* w_out;                            /* [out, in] contiguous          */
+  float* b_out;                            /* [out] or NULL (no bias)       */
+  int64_t T, in, out;
+  uint64_t ctr0_w, ctr0_b;                 /* first Philox block of each    */
+} efl_dp_seq;
+int64_t efl_dp_seq_work_elems(const efl_dp_seq* layers, int64_t nlayers, int64_t B, int64_t rows);
+int64_t efl_dp_seq_partial_elems(const efl_dp_seq* layers, int64_t nlayers, int64_t B, int64_t rows);
+int efl_dp_seq_sqnorm(const efl_dp_seq* layers, int64_t nlayers, int64_t B, int64_t rows, double* work,
+                      int64_t slot0, int64_t slots, void* stream);
+int efl_dp_seq_clip_sum(const efl_dp_seq* layers, int64_t nlayers, int64_t B, int64_t rows, int clip_mode,
+                        float l2_norm_clip, int mode, float sigma, float divisor, uint64_t seed,
+                        float* scales, double* work, int64_t work_elems, float* partials,
+                        int64_t partial_elems, void* stream);
+
 /* efl.metrics.auc: tf.metrics.auc of TF 1.15 as a running histogram (csrc/auc.hip). With
  * T = num_thresholds in [2, 4096]: thr[0] = -1e-7, thr[T - 1] = 1 + 1e-7, thr[i] = i / (T - 1), each formed
  * in double and rounded once to float. An element is predicted positive at threshold t iff

@@ -20,6 +20,9 @@
            table, the WHOLE call: the 256 ids' sort (one launch) and the noise of 16,000,000 floats (one
            launch), against efl_dp_noise over as many floats, HIP events around `--inner` calls, in alternating
            rounds. The C ABI has no entry for the noise launch alone; a kernel trace splits the call.
+           --model seq_mlp is a behaviour-sequence tower: a [256, 64, 128] input, Linear 128 -> 128 twice at
+           every position, the mean over the 64 positions, Linear 128 -> 2. Under "factored" the two position-wise
+           layers take csrc/dpseq.hip (P = 64 rows per microbatch), the head csrc/dpdense.hip, one shared norm.
   kernels  efl_dp_clip_sum alone at [256, 1 Mi] float32 (clip mode 1: the norm pass reads the stack
            once, the sum pass once more; clip mode 0: one read), HIP events around `--inner` calls,
            as a fraction of the 8 TB/s HBM peak: algorithmic bytes (reads of the stack + one write of
@@ -44,7 +47,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--inner", type=int, default=20)
 ap.add_argument("--batch", type=int, default=256)
-ap.add_argument("--model", choices=["dp_cnn", "criteo_mlp", "wide_mlp", "criteo_embed"], default="dp_cnn")
+ap.add_argument("--model", choices=["dp_cnn", "criteo_mlp", "wide_mlp", "criteo_embed", "seq_mlp"], default="dp_cnn")
 ap.add_argument("--loop-rounds", type=int, default=None, help='rounds of the "loop" path (default: --rounds)')
 ap.add_argument("--paths", default="loop,batched,factored",
                 help="the microbatch_gradients paths to time, the first the one the others are compared with")
@@ -89,9 +92,22 @@ class CriteoEmbed(nn.Module):
         return self.mlp(torch.cat([t(ids[:, i:i + 1]) for i, t in enumerate(self.tables)], 1))
 
 
+class SeqMlp(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.tower = nn.Sequential(nn.Linear(128, 128), nn.ReLU(), nn.Linear(128, 128), nn.ReLU())
+        self.head = nn.Linear(128, 2)
+
+    def forward(self, seq):
+        return self.head(self.tower(seq).mean(1))
+
+
 if args.model == "criteo_embed":
     model = CriteoEmbed().to(dev)
     x = torch.stack([torch.randint(0, v, (args.batch,), device=dev) for v in TABLES], 1)
+elif args.model == "seq_mlp":
+    model = SeqMlp().to(dev)
+    x = torch.randn(args.batch, 64, 128, device=dev)
 elif args.model != "dp_cnn":
     widths = (181, 64, 16, 2) if args.model == "criteo_mlp" else (1024, 1024, 1024, 10)
     model = nn.Sequential(*[m for i, o in zip(widths, widths[1:]) for m in (nn.Linear(i, o), nn.ReLU())][:-1]).to(dev)
