@@ -81,6 +81,12 @@ _SIGS = {
     "efl_dp_seq_sqnorm": ([_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp], _i32),
     "efl_dp_seq_clip_sum": ([_vp, _i64, _i64, _i64, _i32, ctypes.c_float, _i32, ctypes.c_float, ctypes.c_float,
                              ctypes.c_uint64, _vp, _vp, _i64, _vp, _i64, _vp], _i32),
+    # the same step for LayerNorm / GroupNorm scales and biases: layers is a host array of DpNorm
+    "efl_dp_norm_work_elems": ([_vp, _i64, _i64, _i64], _i64),
+    "efl_dp_norm_scratch_bytes": ([_vp, _i64, _i64, _i64], _i64),
+    "efl_dp_norm_sqnorm": ([_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp], _i32),
+    "efl_dp_norm_clip_sum": ([_vp, _i64, _i64, _i64, _i32, ctypes.c_float, _i32, ctypes.c_float, ctypes.c_float,
+                              ctypes.c_uint64, _vp, _vp, _i64, _vp, _i64, _vp], _i32),
     # efl.metrics: the thresholded AUC's histogram and value, and the grouped AUC (csrc/auc.hip)
     "efl_auc_work_elems": ([_i64, _i32], _i64),
     "efl_auc_update": ([_vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp, _i64, _vp], _i32),
@@ -183,6 +189,15 @@ class DpSeq(ctypes.Structure):
     _fields_ = [("x", _vp), ("x_row_stride", _i64), ("d", _vp), ("d_row_stride", _i64), ("w_out", _vp),
                 ("b_out", _vp), ("T", _i64), ("in_", _i64), ("out", _i64), ("ctr0_w", ctypes.c_uint64),
                 ("ctr0_b", ctypes.c_uint64)]
+
+
+class DpNorm(ctypes.Structure):
+    """efl_dp_norm (include/efl_hip.h): one normalisation layer of efl_dp_norm_clip_sum, its input x and the
+    gradient d of the summed loss by its output ([B, T, C] rows for kind 0, contiguous [B, C, L] for kind 1),
+    and its [C] / [C] outputs."""
+    _fields_ = [("x", _vp), ("x_row_stride", _i64), ("d", _vp), ("d_row_stride", _i64), ("w_out", _vp),
+                ("b_out", _vp), ("kind", ctypes.c_int32), ("groups", ctypes.c_int32), ("T_or_L", _i64), ("C", _i64),
+                ("eps", ctypes.c_double), ("ctr0_w", ctypes.c_uint64), ("ctr0_b", ctypes.c_uint64)]
 
 
 DP_SEQ_MAX_ROWS = 8192          # r T of one layer: (example, position) rows per microbatch of efl_dp_seq_clip_sum

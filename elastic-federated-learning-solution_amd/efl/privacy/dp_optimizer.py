@@ -46,8 +46,12 @@ of tables and an MLP runs under one norm. A Linear of `dense_layers=` applied at
 (input [B, *, in]: T positions per example) is the fourth (csrc/dpseq.hip's efl_dp_seq_clip_sum): a microbatch
 of r examples has P = r T rows (at most 8,192), its norm is sum Gd (Gx + 1) over the [P, P] Grams of the rows
 of X and of D, formed in 64 x 64 blocks on the fp64 matrix cores and never stored, and its sum is the GEMM
-D^T diag(s) X over all B T rows, split over groups of microbatches. A model with any other variable is out of
-its scope.
+D^T diag(s) X over all B T rows, split over groups of microbatches. torch.nn.LayerNorm (over the last
+dimension) and torch.nn.GroupNorm modules given as `norm_layers=` are the fifth (csrc/dpnorm.hip's
+efl_dp_norm_clip_sum, `dp_norm_clip_sum_noise`): the gradient of their scale and bias is a column reduction of
+d (x - mean) / sqrt(var + eps) and of d over a microbatch's elements, with the statistics and the sums in
+double; each microbatch's [C] results are stacked (rows x 2 C floats, the only per-microbatch storage of the
+path) and efl_dp_clip_sum adds them. A model with any other variable is out of its scope.
 
 Torch mapping. TF optimisers get their variables at minimize time; torch ones at construction.
 These classes take either: `params` (as `params=`, or first positional with the DP arguments as
@@ -119,9 +123,10 @@ def set_microbatch_gradients(name: str) -> None:
     """The process default of the DP optimisers' `microbatch_gradients` keyword: "loop" (one
     autograd.grad and one torch clip-and-add per microbatch, the default), "batched" (one batched
     autograd.grad, then efl_dp_clip_sum over the stacked gradients) or "factored" (one ordinary
-    autograd.grad to the outputs of the layers registered as dense_layers=, conv_layers= and
-    embedding_layers=, then efl_dp_dense_clip_sum, efl_dp_conv_clip_sum and efl_dp_embed_clip_sum under one
-    shared clip norm; a model with any other variable is refused)."""
+    autograd.grad to the outputs of the layers registered as dense_layers=, conv_layers=,
+    embedding_layers= and norm_layers=, then efl_dp_dense_clip_sum, efl_dp_seq_clip_sum, efl_dp_conv_clip_sum,
+    efl_dp_embed_clip_sum and efl_dp_norm_clip_sum under one shared clip norm; a model with any other
+    variable is refused)."""
     global _microbatch_gradients
     _microbatch_gradients = _resolve_microbatch_gradients(name)
 
@@ -367,7 +372,7 @@ def dp_dense_clip_sum_noise(layers, rows: int, l2_norm_clip, mode: int, sigma: f
     for x, d, has_bias in layers:
         seed, cw = (stream or _stream).take(d.shape[-1] * x.shape[-1])
         ctrs.append((cw, (stream or _stream).take(d.shape[-1])[1] if has_bias else 0))
-    outs, _, _, scales = _factored_clip_sum(layers, [], rows, l2_norm_clip, mode, sigma, divisor, seed, ctrs, [], scales)
+    outs, _, _, _, scales = _factored_clip_sum(layers, [], rows, l2_norm_clip, mode, sigma, divisor, seed, ctrs, [], scales)
     if return_scales:
         return outs, torch.ones(rows, device=layers[0][0].device) if scales is None else scales
     return outs
@@ -612,26 +617,143 @@ def dp_embed_clip_sum_noise(layers, rows: int, l2_norm_clip, mode: int, sigma: f
     return outs
 
 
+def _check_norm_layers(layers, rows, who):
+    """[(x, d, has_bias, groups | None, eps)] with detached tensors: a LayerNorm over the last dimension
+    (groups None) gives x and d [B, *, C], flattened to [B, T, C]; a GroupNorm of `groups` groups gives
+    [B, C, *], flattened to [B, C, L]."""
+    out = []
+    for x, d, has_bias, groups, eps in layers:
+        out.append((lib.as_tensor(x).detach(), lib.as_tensor(d).detach(), bool(has_bias),
+                    None if groups is None else int(groups), float(eps)))
+    dev, B = out[0][0].device, out[0][0].shape[0] if out[0][0].dim() else 0
+    for k, (x, d, has_bias, groups, eps) in enumerate(out):
+        if x.dtype != torch.float32 or d.dtype != torch.float32:
+            raise errors.InvalidArgumentError(f"{who}: x and d must be float32, got {x.dtype} and {d.dtype}")
+        if x.device != dev or d.device != dev or dev.type != "cuda":
+            raise errors.InvalidArgumentError(f"{who}: every x and d lies on one ROCm device")
+        if x.dim() < 2 or x.shape != d.shape or x.shape[0] != B or 0 in x.shape:
+            raise errors.InvalidArgumentError(
+                f"{who}: a norm layer takes x and d of one shape, [B, *, C] (LayerNorm) or [B, C, *] (GroupNorm) with "
+                f"B = {B}, got {tuple(x.shape)} and {tuple(d.shape)}")
+        shape = (B, -1, x.shape[-1]) if groups is None else (B, x.shape[1], -1)
+        out[k] = (x.reshape(shape), d.reshape(shape), has_bias, groups, eps)
+    rows = int(rows)
+    if rows < 1 or B % rows:
+        raise errors.InvalidArgumentError(f"{who}: {rows} microbatches do not divide the batch of {B}")
+    if B // rows > MAX_ROWS_PER_MICROBATCH:
+        raise errors.InvalidArgumentError(f"{who}: {B // rows} examples per microbatch, at most "
+                                          f"{MAX_ROWS_PER_MICROBATCH} (r > {MAX_ROWS_PER_MICROBATCH})")
+    return out, rows
+
+
+def _norm_table(layers, ctrs, rows):
+    """The DpNorm table of checked norm layers with freshly carved outputs and the call's scratch: (table,
+    [(w_grad, b_grad | None)], tensors to keep alive, scratch, its bytes). A channel-last tensor whose
+    positions are contiguous rows at least C apart is taken as it lies (a padded row stride included)."""
+    dev, B, like = layers[0][0].device, layers[0][0].shape[0], []
+    for x, _, has_bias, groups, _ in layers:
+        like += [torch.empty(x.shape[2 if groups is None else 1], device="meta")] * (2 if has_bias else 1)
+    flat = iter(lib._carve(like, torch.float32, dev))
+    arr, outs, keep = (lib.DpNorm * len(layers))(), [], []
+
+    def rows_of(t):     # the flattened [B T, C] rows and their stride
+        _, T, width = t.shape
+        s = t.stride(1) if T > 1 else t.stride(0) if B > 1 else width
+        if t.stride(2) != 1 or s < width or (B > 1 and T > 1 and t.stride(0) != T * s) or t.data_ptr() % 4:
+            t, s = t.contiguous(), width
+        return t, s
+
+    for rec, (x, d, has_bias, groups, eps), (cw, cb) in zip(arr, layers, ctrs):
+        if groups is None:
+            (x, rec.x_row_stride), (d, rec.d_row_stride) = rows_of(x), rows_of(d)
+            rec.kind, rec.groups, rec.T_or_L, rec.C = 0, 1, x.shape[1], x.shape[2]
+        else:
+            x, d = x.contiguous(), d.contiguous()
+            rec.kind, rec.groups, rec.T_or_L, rec.C = 1, groups, x.shape[2], x.shape[1]
+        keep += [x, d]
+        w, b = next(flat), next(flat) if has_bias else None
+        rec.x, rec.d, rec.w_out, rec.b_out, rec.eps = x.data_ptr(), d.data_ptr(), w.data_ptr(), None if b is None else b.data_ptr(), eps
+        rec.ctr0_w, rec.ctr0_b = cw, cb
+        outs.append((w, b))
+    nbytes = _elems(lib.raw().efl_dp_norm_scratch_bytes(arr, len(layers), B, rows))
+    return arr, outs, keep, torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev), nbytes
+
+
+def _norm_clip_sum(layers, rows, l2_norm_clip, mode, sigma, divisor, seed, ctrs, scales, table=None):
+    """efl_dp_norm_clip_sum over checked norm layers; ctrs: per layer the first Philox block of (weight,
+    bias); table: their _norm_table when the caller has made it. Returns ([(w_grad, b_grad | None)],
+    scales | None)."""
+    dev, B, raw = layers[0][0].device, layers[0][0].shape[0], lib.raw()
+    arr, outs, keep, scratch, nbytes = table or _norm_table(layers, ctrs, rows)
+    clip_mode = 2 if scales is not None else 0 if l2_norm_clip is None else 1
+    work, work_elems = None, 0
+    if clip_mode == 2:
+        scales = lib.as_tensor(scales).detach().to(dev, torch.float32).contiguous()
+        if scales.shape != (rows,):
+            raise errors.InvalidArgumentError(f"dp_norm_clip_sum_noise: scales must be [{rows}]")
+    elif clip_mode == 1:
+        work_elems = _elems(raw.efl_dp_norm_work_elems(arr, len(layers), B, rows))
+        work = torch.empty(max(work_elems, 1), dtype=torch.float64, device=dev)
+        scales = torch.empty(rows, dtype=torch.float32, device=dev)
+    lib.check(raw.efl_dp_norm_clip_sum(arr, len(layers), B, rows, clip_mode, float(l2_norm_clip or 0.0), int(mode),
+                                       float(sigma), float(divisor), seed,
+                                       None if scales is None else scales.data_ptr(),
+                                       None if work is None else work.data_ptr(), work_elems, scratch.data_ptr(),
+                                       nbytes, lib.stream_handle(dev)))
+    return outs, scales
+
+
+def _norm_numels(layers):
+    return [(x.shape[2 if groups is None else 1],) * 2 if has_bias else (x.shape[2 if groups is None else 1], 0)
+            for x, _, has_bias, groups, _ in layers]
+
+
+@exporter.export("privacy.dp_norm_clip_sum_noise")
+def dp_norm_clip_sum_noise(layers, rows: int, l2_norm_clip, mode: int, sigma: float, divisor: float = 1.0,
+                           stream: NoiseStream | None = None, scales=None, return_scales: bool = False):
+    """efl_dp_norm_clip_sum: a DP-SGD step's clipped, summed, noised and divided gradients of the scale
+    (weight) and bias of per-example normalisation layers from their inputs and output gradients. `layers`
+    is a list of (x, d, has_bias, groups, eps): float32 ROCm tensors of one shape, d the gradient of the SUM
+    of the per-example losses by the layer's output. groups None is a torch.nn.LayerNorm over the last
+    dimension (x [B, *, C], statistics per row); an int G a torch.nn.GroupNorm of G groups (x [B, C, *],
+    statistics per example and group). Microbatch i is the B / rows (at most 16) consecutive examples from
+    i * B / rows. Returns [(w_grad [C], b_grad [C] | None)]: noise(sum_i scale_i sum d xh) / divisor and
+    noise(sum_i scale_i sum d) / divisor, xh = (x - mean) / sqrt(var + eps) with the statistics in double;
+    mode, sigma, divisor, scales, return_scales and the stream positions (one take(numel) per variable,
+    weight then bias, in layer order) are dp_dense_clip_sum_noise's."""
+    layers = list(layers)
+    if not layers:
+        return ([], None) if return_scales else []
+    layers, rows = _check_norm_layers(layers, rows, "dp_norm_clip_sum_noise")
+    seed, ctrs = _take_layers(_norm_numels(layers), stream or _stream)
+    outs, scales = _norm_clip_sum(layers, rows, l2_norm_clip, mode, sigma, divisor, seed, ctrs, scales)
+    if return_scales:
+        return outs, torch.ones(rows, device=layers[0][0].device) if scales is None else scales
+    return outs
+
+
 def _factored_clip_sum(dense, conv, rows, l2_norm_clip, mode, sigma, divisor, seed, dctrs, cctrs, scales,
-                       embed=(), ectrs=()):
-    """Checked dense, conv and embedding layers under ONE norm: (dense outs, conv outs, embedding outs,
-    scales | None). With more than one family and no given scales, all write their norm slots into one work
-    buffer [rows, slots] (dense, then conv, then embedding), efl_dp_scales makes the scales, and every sum
-    runs with them (clip_mode 2). The dense layers over sequences (x [B, T, in]) are a family of their own
-    (csrc/dpseq.hip), their slots after the 2-D dense layers'; their outputs come back in `dense`'s order."""
+                       embed=(), ectrs=(), norm=(), nctrs=()):
+    """Checked dense, conv, embedding and norm layers under ONE norm: (dense outs, conv outs, embedding outs,
+    norm outs, scales | None). With more than one family and no given scales, all write their norm slots into
+    one work buffer [rows, slots] (dense, then conv, then embedding, then norm), efl_dp_scales makes the
+    scales, and every sum runs with them (clip_mode 2). The dense layers over sequences (x [B, T, in]) are a
+    family of their own (csrc/dpseq.hip), their slots after the 2-D dense layers'; their outputs come back in
+    `dense`'s order."""
     seq_at = [k for k, (x, _, _) in enumerate(dense) if x.dim() == 3]
     seq, sctrs = [dense[k] for k in seq_at], [dctrs[k] for k in seq_at]
     dense_at = [k for k in range(len(dense)) if k not in seq_at]
     dense, dctrs = [dense[k] for k in dense_at], [dctrs[k] for k in dense_at]
-    dtab = stab = ctab = etab = None
-    if (bool(dense) + bool(seq) + bool(conv) + bool(embed)) > 1 and scales is None and l2_norm_clip is not None:
-        first = dense[0][0] if dense else seq[0][0] if seq else conv[0][0]
+    dtab = stab = ctab = etab = ntab = None
+    if (bool(dense) + bool(seq) + bool(conv) + bool(embed) + bool(norm)) > 1 and scales is None and l2_norm_clip is not None:
+        first = dense[0][0] if dense else seq[0][0] if seq else conv[0][0] if conv else norm[0][0]
         dev, B, raw, h = first.device, first.shape[0], lib.raw(), lib.stream_handle(first.device)
         dtab, ctab, etab = dense and _dense_table(dense, dctrs), conv and _conv_table(conv, cctrs), embed and _embed_table(embed, ectrs)
-        stab = seq and _seq_table(seq, sctrs)
+        stab, ntab = seq and _seq_table(seq, sctrs), norm and _norm_table(norm, nctrs, rows)
         ns = _elems(raw.efl_dp_seq_work_elems(stab[0], len(seq), B, rows)) // rows if seq else 0
         nc = _elems(raw.efl_dp_conv_work_elems(ctab[0], len(conv), rows)) // rows if conv else 0
-        slots = len(dense) + ns + nc + len(embed)
+        nn = _elems(raw.efl_dp_norm_work_elems(ntab[0], len(norm), B, rows)) // rows if norm else 0
+        slots = len(dense) + ns + nc + len(embed) + nn
         work = torch.empty(rows * slots, dtype=torch.float64, device=dev)
         scales = torch.empty(rows, dtype=torch.float32, device=dev)
         if dense:
@@ -642,8 +764,11 @@ def _factored_clip_sum(dense, conv, rows, l2_norm_clip, mode, sigma, divisor, se
             lib.check(raw.efl_dp_conv_sqnorm(ctab[0], len(conv), B, rows, work.data_ptr(), len(dense) + ns, slots, h))
         if embed:
             lib.check(raw.efl_dp_embed_sqnorm(etab[0], len(embed), B, rows, work.data_ptr(), len(dense) + ns + nc, slots, h))
+        if norm:
+            lib.check(raw.efl_dp_norm_sqnorm(ntab[0], len(norm), B, rows, work.data_ptr(), slots - nn, slots,
+                                             ntab[3].data_ptr(), ntab[4], h))
         lib.check(raw.efl_dp_scales(work.data_ptr(), slots, rows, float(l2_norm_clip), scales.data_ptr(), h))
-    douts = couts = eouts = []
+    douts = couts = eouts = nouts = []
     if dense:                               # one family alone takes its own norm pass (clip_mode 1)
         douts, scales = _dense_clip_sum(dense, rows, l2_norm_clip, mode, sigma, divisor, seed, dctrs, scales, dtab or None)
     if seq:
@@ -656,23 +781,26 @@ def _factored_clip_sum(dense, conv, rows, l2_norm_clip, mode, sigma, divisor, se
         couts, scales = _conv_clip_sum(conv, rows, l2_norm_clip, mode, sigma, divisor, seed, cctrs, scales, ctab or None)
     if embed:
         eouts, scales = _embed_clip_sum(embed, rows, l2_norm_clip, mode, sigma, divisor, seed, ectrs, scales, etab or None)
-    return douts, couts, eouts, scales
+    if norm:
+        nouts, scales = _norm_clip_sum(norm, rows, l2_norm_clip, mode, sigma, divisor, seed, nctrs, scales, ntab or None)
+    return douts, couts, eouts, nouts, scales
 
 
 @exporter.export("privacy.dp_factored_clip_sum_noise")
 def dp_factored_clip_sum_noise(dense_layers, conv_layers, rows: int, l2_norm_clip, mode: int, sigma: float,
                                divisor: float = 1.0, stream: NoiseStream | None = None, scales=None,
-                               return_scales: bool = False, *, embedding_layers=None):
-    """dp_dense_clip_sum_noise, dp_conv_clip_sum_noise and dp_embed_clip_sum_noise over one model's layers
-    under ONE shared clip norm: scale_i = clip * min(1 / ||g_i||, 1 / clip) with g_i microbatch i's gradient
-    of ALL the layers' variables. `dense_layers`, `conv_layers` and `embedding_layers` (keyword only) are
-    those functions' lists (any may be empty); the dense variables come first in the stream, then the conv
-    ones, then the tables. Returns (dense_outs, conv_outs), with `embedding_layers` given (dense_outs,
-    conv_outs, embedding_outs), and the scales after them with return_scales."""
-    dense, conv, embed = list(dense_layers), list(conv_layers), list(embedding_layers or ())
+                               return_scales: bool = False, *, embedding_layers=None, norm_layers=None):
+    """dp_dense_clip_sum_noise, dp_conv_clip_sum_noise, dp_embed_clip_sum_noise and dp_norm_clip_sum_noise
+    over one model's layers under ONE shared clip norm: scale_i = clip * min(1 / ||g_i||, 1 / clip) with g_i
+    microbatch i's gradient of ALL the layers' variables. `dense_layers`, `conv_layers`, `embedding_layers`
+    and `norm_layers` (the last two keyword only) are those functions' lists (any may be empty); the dense
+    variables come first in the stream, then the conv ones, then the tables, then the norm layers'. Returns
+    (dense_outs, conv_outs), with `embedding_layers` given embedding_outs after them, with `norm_layers`
+    given norm_outs after those, and the scales last with return_scales."""
+    dense, conv, embed, norm = list(dense_layers), list(conv_layers), list(embedding_layers or ()), list(norm_layers or ())
     who = "dp_factored_clip_sum_noise"
-    tail = () if embedding_layers is None else ([],)
-    if not dense and not conv and not embed:
+    tail = (() if embedding_layers is None else ([],)) + (() if norm_layers is None else ([],))
+    if not dense and not conv and not embed and not norm:
         return ([], [], *tail, None) if return_scales else ([], [], *tail)
     if dense:
         dense, rows = _check_dense_layers(dense, rows, who)
@@ -680,17 +808,20 @@ def dp_factored_clip_sum_noise(dense_layers, conv_layers, rows: int, l2_norm_cli
         conv, rows = _check_conv_layers(conv, rows, who)
     if embed:
         embed, rows = _check_embed_layers(embed, rows, who)
-    firsts = [f[0][0] for f in (dense, conv, embed) if f]
+    if norm:
+        norm, rows = _check_norm_layers(norm, rows, who)
+    firsts = [f[0][0] for f in (dense, conv, embed, norm) if f]
     if any(t.shape[0] != firsts[0].shape[0] or t.device != firsts[0].device for t in firsts):
-        raise errors.InvalidArgumentError(f"{who}: the dense, conv and embedding layers take one batch on one device")
+        raise errors.InvalidArgumentError(f"{who}: the dense, conv, embedding and norm layers take one batch on one device")
     st = stream or _stream
     seed, dctrs = _take_layers([(d.shape[-1] * x.shape[-1], d.shape[-1] if b else 0) for x, d, b in dense], st)
     seed_c, cctrs = _take_layers(_conv_numels(conv), st)
     seed_e, ectrs = _take_layers([(V * d.shape[-1], 0) for _, d, V, _ in embed], st)
-    seed = next(v for v in (seed, seed_c, seed_e) if v is not None)
-    douts, couts, eouts, scales = _factored_clip_sum(dense, conv, rows, l2_norm_clip, mode, sigma, divisor, seed, dctrs,
-                                                     cctrs, scales, embed, [c for c, _ in ectrs])
-    outs = (douts, couts) if embedding_layers is None else (douts, couts, eouts)
+    seed_n, nctrs = _take_layers(_norm_numels(norm), st)
+    seed = next(v for v in (seed, seed_c, seed_e, seed_n) if v is not None)
+    douts, couts, eouts, nouts, scales = _factored_clip_sum(dense, conv, rows, l2_norm_clip, mode, sigma, divisor, seed,
+                                                            dctrs, cctrs, scales, embed, [c for c, _ in ectrs], norm, nctrs)
+    outs = (douts, couts, *(() if embedding_layers is None else (eouts,)), *(() if norm_layers is None else (nouts,)))
     if return_scales:
         return (*outs, torch.ones(rows, device=firsts[0].device) if scales is None else scales)
     return outs
@@ -844,7 +975,9 @@ def make_optimizer_class(cls):
             "batched" / "factored" (keyword only; None: the process default, set_microbatch_gradients).
             dense_layers=, conv_layers= and embedding_layers= (keyword only): the torch.nn.Linear, the
             torch.nn.Conv2d and the torch.nn.Embedding / torch.nn.EmbeddingBag modules "factored" takes its
-            gradients from; each gets a forward hook that keeps its input and output of the current step."""
+            gradients from; each gets a forward hook that keeps its input and output of the current step.
+            norm_layers= (keyword only): the torch.nn.LayerNorm (elementwise_affine, a 1-D normalized_shape, with
+            or without a bias) and torch.nn.GroupNorm (affine) modules, the same way."""
             self._microbatch_gradients = kwargs.pop("microbatch_gradients", None)
             _resolve_microbatch_gradients(self._microbatch_gradients)
             self._dense = {}                # Linear module -> [(detached input, output)] since the last step
@@ -882,6 +1015,20 @@ def make_optimizer_class(cls):
                         f"weighted sum of rows)")
                 self._embed[layer] = []
                 layer.register_forward_hook(self._keep_embed, with_kwargs=True)
+            self._norm = {}                 # LayerNorm / GroupNorm module -> [(detached input, output)]
+            for layer in kwargs.pop("norm_layers", None) or ():
+                if not isinstance(layer, (torch.nn.LayerNorm, torch.nn.GroupNorm)):
+                    raise errors.InvalidArgumentError(
+                        f"norm_layers takes torch.nn.LayerNorm and torch.nn.GroupNorm modules (per-example statistics), "
+                        f"got {type(layer).__name__}")
+                if getattr(layer, "weight", None) is None:
+                    raise errors.InvalidArgumentError(f"norm_layers takes layers with affine parameters, got {layer}")
+                if isinstance(layer, torch.nn.LayerNorm) and len(layer.normalized_shape) != 1:
+                    raise errors.InvalidArgumentError(
+                        f"norm_layers takes a LayerNorm over the last dimension alone, got normalized_shape "
+                        f"{tuple(layer.normalized_shape)}")
+                self._norm[layer] = []
+                layer.register_forward_hook(self._keep_dense)
             if "learning_rate" in kwargs:
                 kwargs["lr"] = kwargs.pop("learning_rate")
             lead = _as_params(args[0]) if args else None
@@ -938,7 +1085,7 @@ def make_optimizer_class(cls):
                     return list(zip(self._factored_gradients(loss, var_list, grad_loss, reduce_func, params, nm,
                                                              batch_size), var_list))
                 finally:                    # the kept inputs and outputs belong to this step alone
-                    for seen in (*self._dense.values(), *self._conv.values(), *self._embed.values()):
+                    for seen in (*self._dense.values(), *self._conv.values(), *self._embed.values(), *self._norm.values()):
                         seen.clear()
             if path == "batched":
                 stacked = self._stacked_gradients(loss, var_list, grad_loss, reduce_func)
@@ -987,7 +1134,8 @@ def make_optimizer_class(cls):
             # a forward pass outside autograd (an evaluation under no_grad) is not part of a step
             if (torch.is_grad_enabled() and output.requires_grad
                     and _resolve_microbatch_gradients(self._microbatch_gradients) == "factored"):
-                (self._dense if layer in self._dense else self._conv)[layer].append((inputs[0].detach(), output))
+                kept = self._dense if layer in self._dense else self._conv if layer in self._conv else self._norm
+                kept[layer].append((inputs[0].detach(), output))
 
         def _keep_embed(self, layer, inputs, kwargs, output):
             if (torch.is_grad_enabled() and output.requires_grad
@@ -998,9 +1146,10 @@ def make_optimizer_class(cls):
                 self._embed[layer].append((ids.detach(), output, plain))
 
         def _factored_gradients(self, loss, var_list, grad_loss, reduce_func, params, nm, batch):
-            """The step's gradients of the registered dense, conv and embedding layers' variables from ONE
+            """The step's gradients of the registered dense, conv, embedding and norm layers' variables from ONE
             ordinary backward to the layers' outputs, then efl_dp_dense_clip_sum (csrc/dpdense.hip),
-            efl_dp_conv_clip_sum (csrc/dpconv.hip) and efl_dp_embed_clip_sum (csrc/dpembed.hip) under one shared norm. Precondition that cannot be
+            efl_dp_conv_clip_sum (csrc/dpconv.hip), efl_dp_embed_clip_sum (csrc/dpembed.hip) and
+            efl_dp_norm_clip_sum (csrc/dpnorm.hip) under one shared norm. Precondition that cannot be
             checked here: the examples are independent in the forward pass (no batch statistics), so
             that row k of d(sum of the loss)/d(output) is example k's own."""
             who = 'microbatch_gradients="factored"'
@@ -1012,7 +1161,7 @@ def make_optimizer_class(cls):
             if callable(reduce_func):
                 raise errors.InvalidArgumentError(f"{who}: a callable REDUCE needs the per-microbatch losses")
             owner = {}
-            for layer in (*self._dense, *self._conv, *self._embed):
+            for layer in (*self._dense, *self._conv, *self._embed, *self._norm):
                 owner[layer.weight] = (layer, 0)
                 if getattr(layer, "bias", None) is not None:
                     owner[layer.bias] = (layer, 1)
@@ -1021,14 +1170,15 @@ def make_optimizer_class(cls):
                 if v not in owner:
                     raise errors.InvalidArgumentError(
                         f"{who}: variable {i} of var_list {tuple(v.shape)} is not the weight or bias of a layer "
-                        f"given as dense_layers=, conv_layers= or embedding_layers=")
+                        f"given as dense_layers=, conv_layers=, embedding_layers= or norm_layers=")
                 used.setdefault(owner[v][0], [None, None])[owner[v][1]] = i
             layers = []
             for layer, (wi, bi) in used.items():
                 if wi is None:
                     raise errors.InvalidArgumentError(f"{who}: the bias of {layer} is in var_list without its weight")
-                is_conv = layer in self._conv
-                seen = (self._embed if layer in self._embed else self._conv if is_conv else self._dense)[layer]
+                is_conv, is_norm = layer in self._conv, layer in self._norm
+                seen = (self._embed if layer in self._embed else self._conv if is_conv else self._norm if is_norm
+                        else self._dense)[layer]
                 if len(seen) != 1:
                     raise errors.InvalidArgumentError(
                         f"{who}: {layer} ran {len(seen)} times since the last step; each layer runs once")
@@ -1046,22 +1196,26 @@ def make_optimizer_class(cls):
                 elif ((x.dim() != 4 if is_conv else x.dim() < 2) or x.shape[0] != batch or x.dtype != torch.float32
                         or out.dtype != torch.float32):
                     raise errors.InvalidArgumentError(
-                        f"{who}: {layer} takes a float32 {'[B, Cin, H, W]' if is_conv else '[B, in] or [B, *, in]'} input with "
+                        f"{who}: {layer} takes a float32 {'[B, Cin, H, W]' if is_conv else '[B, ...]' if is_norm else '[B, in] or [B, *, in]'} input with "
                         f"B = {batch} per-example losses, got {x.dtype} {tuple(x.shape)}")
                 layers.append((layer, wi, bi, x, out))
             go = torch.ones_like(loss) if grad_loss is None else grad_loss.reshape(loss.shape)
             ds = torch.autograd.grad(loss, [l[4] for l in layers], grad_outputs=go, retain_graph=True, allow_unused=True)
-            dense, conv, embed = [], [], []     # (position in `layers`, record)
+            dense, conv, embed, norm = [], [], [], []     # (position in `layers`, record)
             for k, ((layer, _, bi, x, out), d) in enumerate(zip(layers, ds)):
                 d = d if d is not None else torch.zeros_like(out)
-                if layer in self._embed:
+                if layer in self._norm:
+                    norm.append((k, (x, d, bi is not None, getattr(layer, "num_groups", None), layer.eps)))
+                elif layer in self._embed:
                     mean = getattr(layer, "mode", "sum") == "mean"
                     embed.append((k, (x, d, layer.num_embeddings, 1.0 / x.shape[1] if mean else 1.0)))
                 elif layer in self._conv:
                     conv.append((k, (x, d, bi is not None, layer.kernel_size, layer.stride, layer.padding, layer.dilation)))
                 else:
                     dense.append((k, (x, d, bi is not None)))
-            drecs, crecs, erecs = [r for _, r in dense], [r for _, r in conv], [r for _, r in embed]
+            drecs, crecs, erecs, nrecs = ([r for _, r in f] for f in (dense, conv, embed, norm))
+            if nrecs:
+                nrecs, nm = _check_norm_layers(nrecs, nm, who)
             if erecs:
                 erecs, nm = _check_embed_layers(erecs, nm, who)
             if drecs:
@@ -1071,11 +1225,13 @@ def make_optimizer_class(cls):
             takes = [_stream.take(v.numel()) for v in var_list]          # as the loop: var_list order
             ctr = [(takes[wi][1], takes[bi][1] if bi is not None else 0) for _, wi, bi, _, _ in layers]
             clip, mode, sigma = (params, 1, q._stddev) if type(q) is GaussianSumQuery else (None, 0, q._noise_multiplier)
-            douts, couts, eouts, _ = _factored_clip_sum(drecs, crecs, nm, clip, mode, sigma, float(nm), takes[0][0],
-                                                        [ctr[k] for k, _ in dense], [ctr[k] for k, _ in conv], None,
-                                                        erecs, [ctr[k][0] for k, _ in embed])
+            douts, couts, eouts, nouts, _ = _factored_clip_sum(drecs, crecs, nm, clip, mode, sigma, float(nm), takes[0][0],
+                                                               [ctr[k] for k, _ in dense], [ctr[k] for k, _ in conv], None,
+                                                               erecs, [ctr[k][0] for k, _ in embed],
+                                                               nrecs, [ctr[k] for k, _ in norm])
             final = [None] * len(var_list)
-            for k, (w, b) in zip([k for k, _ in dense + conv + embed], [*douts, *couts, *((t, None) for t in eouts)]):
+            for k, (w, b) in zip([k for k, _ in dense + conv + embed + norm],
+                                 [*douts, *couts, *((t, None) for t in eouts), *nouts]):
                 _, wi, bi, _, _ = layers[k]
                 final[wi] = w
                 if bi is not None:

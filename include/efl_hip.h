@@ -1036,6 +1036,64 @@ int efl_dp_seq_clip_sum(const efl_dp_seq* layers, int64_t nlayers, int64_t B, in
                         float* scales, double* work, int64_t work_elems, float* partials,
                         int64_t partial_elems, void* stream);
 
+/* The same step for the scale (weight) and bias of per-example normalisation layers (csrc/dpnorm.hip).
+ * kind 0, channel-last (torch.nn.LayerNorm over the last dimension): x and d [B, T, C], row p = b T + t at
+ * x + p x_row_stride and d + p d_row_stride (a padded stride is taken as it lies); an element's statistics
+ * group is its row, n = C; groups must be 1. kind 1, channel-first (torch.nn.GroupNorm): x and d [B, C, L]
+ * contiguous (the strides are ignored); the statistics group (b, g) is the C / groups channels of group g
+ * times the L positions, n = (C / groups) L contiguous floats. With mu the mean and var the biased variance
+ * over the group and xh = (x - mu) / sqrt(var + eps), microbatch i (the r = B / rows consecutive examples from
+ * i r, 1 <= r <= 16) has ggamma_i[c] = sum d xh and gbeta_i[c] = sum d over its elements of channel c, and
+ *   S_i = sum over layers of sum_c ggamma_i[c]^2 + beta sum_c gbeta_i[c]^2,   beta = 1 with a bias, 0 without.
+ * Rounding contract.
+ *   Scales: (mu, 1 / sqrt(var + eps)) per statistics group in double, two passes (the mean, then
+ *   sum (x - mu)^2), stored as doubles; d (x - mu) rstd formed and summed in double over exactly widened
+ *   fp32 inputs, a lane's terms in order, then a fixed tree; S_i from the double sums, one slot per
+ *   workgroup (a tile of 256 columns of a channel-last layer, 4 channels of a channel-first one), no
+ *   atomics: the same bytes on every run. S_i is within 2^-32 sum_c [(sum |d| |xh|)^2 + beta (sum |d|)^2] of
+ *   the exact one while (N + n) (1 + |mu| / sigma) < 2^20, N a microbatch's elements per channel and n a
+ *   group's. scale = (float)(clip *
+ *   min(1 / sqrt(S_i), 1 / clip)) rounded once; S_i = 0 gives 1 and an infinite S_i gives 0.
+ *   Sum: every microbatch's ggamma and gbeta are rounded once to fp32 into a stack [rows, .] inside
+ *   `scratch`, and efl_dp_clip_sum over that stack (clip_mode 2 with the scales, 0 without) adds the rows in
+ *   order, noises and divides. Per element
+ *   |got - exact| <= (rows + 4) 2^-24 (sum_i s_i sum |d xh| + |noise|) / |divisor|   (the bias: sum |d|).
+ * w_out and b_out [C] (b_out NULL: no bias, beta = 0) are 16-byte aligned; element j of each takes normal
+ * j % 4 of block ctr0_w / ctr0_b + j / 4 under `seed`.
+ * efl_dp_norm_work_elems: doubles of `work` (rows x the layers' slots: ceil(C / 256) for kind 0,
+ * ceil(C / 4) for kind 1; clip_mode 1 only). efl_dp_norm_scratch_bytes: bytes of `scratch` (always needed,
+ * 16-byte aligned): 16 per statistics group (B T or B groups per layer), then the stack, rows x the sum over
+ * layers of pad4(C) (twice with a bias) floats. efl_dp_norm_sqnorm writes the layers' slots
+ * [slot0, slot0 + efl_dp_norm_work_elems / rows) of a shared work buffer (above); it uses the statistics part
+ * of the same scratch. clip_mode, l2_norm_clip, mode, sigma, divisor, seed and scales are
+ * efl_dp_dense_clip_sum's. `layers` is a HOST array; it travels to the kernels by value, 24 layers per
+ * launch: no device allocation, no copy, stream-ordered. The outputs and the scratch must not overlap the
+ * inputs. nlayers == 0 is a no-op.
+ * EFL_E_INVALID_ARGUMENT, before any HIP call, for: a null table or buffer; x or d not 4-byte, w_out or b_out
+ * not 16-byte aligned; an unknown kind; C < 1; T_or_L < 1; groups < 1, not dividing C, or not 1 for kind 0;
+ * eps negative or not finite; a row stride below C (kind 0); rows not dividing B; B / rows > 16; an unknown
+ * clip_mode or mode; a zero divisor; a null, misaligned or short work (clip_mode 1), scales (clip_mode 1, 2)
+ * or scratch. */
+typedef struct efl_dp_norm {
+  const float* x;  int64_t x_row_stride;   /* layer input; the stride of kind 0's rows */
+  const float* d;  int64_t d_row_stride;   /* dLoss/d(output), laid out as x          */
+  float* w_out;                            /* [C]                                     */
+  float* b_out;                            /* [C] or NULL (no bias)                   */
+  int32_t kind;                            /* 0 channel-last, 1 channel-first         */
+  int32_t groups;                          /* kind 1: G; kind 0: 1                    */
+  int64_t T_or_L, C;                       /* positions per example, channels         */
+  double eps;
+  uint64_t ctr0_w, ctr0_b;                 /* first Philox block of each              */
+} efl_dp_norm;
+int64_t efl_dp_norm_work_elems(const efl_dp_norm* layers, int64_t nlayers, int64_t B, int64_t rows);
+int64_t efl_dp_norm_scratch_bytes(const efl_dp_norm* layers, int64_t nlayers, int64_t B, int64_t rows);
+int efl_dp_norm_sqnorm(const efl_dp_norm* layers, int64_t nlayers, int64_t B, int64_t rows, double* work,
+                       int64_t slot0, int64_t slots, void* scratch, int64_t scratch_bytes, void* stream);
+int efl_dp_norm_clip_sum(const efl_dp_norm* layers, int64_t nlayers, int64_t B, int64_t rows, int clip_mode,
+                         float l2_norm_clip, int mode, float sigma, float divisor, uint64_t seed,
+                         float* scales, double* work, int64_t work_elems, void* scratch,
+                         int64_t scratch_bytes, void* stream);
+
 /* efl.metrics.auc: tf.metrics.auc of TF 1.15 as a running histogram (csrc/auc.hip). With
  * T = num_thresholds in [2, 4096]: thr[0] = -1e-7, thr[T - 1] = 1 + 1e-7, thr[i] = i / (T - 1), each formed
  * in double and rounded once to float. An element is predicted positive at threshold t iff
